@@ -8,6 +8,14 @@ resident in HBM. N GPUs (torchrun, one rank per GPU): every rank hashes its
 own 1 M-frame batch (frames are independent -> weak scaling, no collective on
 the data path; the only collectives are the timing barrier/max).
 
+A plain run does only what the headline figure needs: it builds the batch,
+runs the warm-up and the timed steps, writes the last step's outputs with
+--dump-outputs DIR, and prints the result line. --full adds everything else
+the benchmark measures or checks, each after the timed steps: the oracle
+parity sample, the per-step pass, the same-box read roof, the host-inclusive
+block, the CPU baseline, cfg5's verify windows, the cfg4 strong-scaling block
+and its single-GPU proxy (the --no-* options drop single blocks of it).
+
 Prints ONE JSON line on rank 0. Extra diagnostics go to stderr.
 """
 from __future__ import annotations
@@ -44,6 +52,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=15)  # the first ~10 cfg3 launches run 1-4% slower (clocks settling)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check: oracle parity sample, "
+                         "per-step pass, read roof, host-inclusive block, CPU baseline, cfg5 verify windows, the "
+                         "cfg4 strong-scaling block and its proxy (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (the timed call's output arrays) "
+                         "as DIR/<name>.npy in float64, ranks above 0 as DIR/<name>.rank<r>.npy")
     ap.add_argument("--verify", action="store_true", help="time the RX verify kernel instead of TX")
     ap.add_argument("--pay", action="store_true", help="with --verify: also emit payload states (RX file-CRC by-product)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -65,7 +80,10 @@ def parse():
                          "time (the block follows ~20 s of host-side work with the GPU idle; with 5 launches of "
                          "warm-up it ran 1%% slower than cfg4 alone, with 100 ms 0.5%% faster: "
                          "profiles/r06_ab_cfg4_block.jsonl)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.with_cfg4_strong or args.cfg4_alloc_first):
+        ap.error("--with-cfg4-strong and --cfg4-alloc-first ask for the cfg4 block, which only a --full run times")
+    return args
 
 
 def make_frames(torch, dev, n, payload, explicit, first_index, seed):
@@ -508,6 +526,28 @@ def verify_windows(torch, vc, flat, dev, stream):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, rank, outputs):
+    """--dump-outputs: the arrays the timed call's caller receives, as its
+    last timed step left them, one DIR/<name>.npy each (float64: exact for the
+    32-bit CRC words and the flags). `outputs` maps a name to a device tensor
+    or None. Together at most DUMP_MAX_BYTES: an array over its share is
+    written as a fixed, seeded sample of its elements, in index order. The
+    frames are seeded, so the same arguments give the same files."""
+    os.makedirs(dirname, exist_ok=True)
+    outputs = {k: t for k, t in outputs.items() if t is not None}
+    share = DUMP_MAX_BYTES // max(len(outputs), 1) // 8  # float64 elements per array
+    for name, t in outputs.items():
+        a = t.cpu().numpy().reshape(-1)
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)  # CRC words
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0xD0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a.astype(np.float64))
+
+
 def _free_port() -> int:
     import socket
 
@@ -685,7 +725,8 @@ def main():
     import val_protocol_amd.crc as vc
 
     vc.init(gpu)
-    want_strong = (args.config == "cfg3" or args.with_cfg4_strong) and not args.no_cfg4_strong \
+    full = args.full  # everything beyond the timed steps and the result line
+    want_strong = full and (args.config == "cfg3" or args.with_cfg4_strong) and not args.no_cfg4_strong \
         and args.config != "cfg4" and not args.verify and not args.sort_frames
     # --cfg4-alloc-first: the cfg4 block's buffer is placed before the headline's (diagnostic A/B)
     w4 = build_workload(torch, dev, "cfg4", rank, world, False, vc) if want_strong and args.cfg4_alloc_first else None
@@ -722,18 +763,26 @@ def main():
 
     stream = torch.cuda.current_stream()
     elapsed, kern_ms = timed_steps(torch, dist, world, step, args.steps, args.warmup, stream)
-    # per-step spread, from a short untimed pass with an event pair per step
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 5))]
-    for a, b in evs:
-        a.record(stream)
-        step()
-        b.record(stream)
-    torch.cuda.synchronize()
-    print("[bench] per-step ms (untimed pass): " + " ".join(f"{a.elapsed_time(b):.4f}" for a, b in evs), file=sys.stderr)
+    if args.dump_outputs:  # the last timed step's outputs, before anything else launches
+        if args.verify:
+            dump_outputs(args.dump_outputs, rank, {"ok": ok, "nbad": nbad, "header_crc": hdr, "payload_state": pay})
+        else:
+            dump_outputs(args.dump_outputs, rank, {"crc": crc, "header_crc": hdr})
+    if full:
+        # per-step spread, from a short untimed pass with an event pair per step
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(min(args.steps, 5))]
+        for a, b in evs:
+            a.record(stream)
+            step()
+            b.record(stream)
+        torch.cuda.synchronize()
+        print("[bench] per-step ms (untimed pass): " + " ".join(f"{a.elapsed_time(b):.4f}" for a, b in evs),
+              file=sys.stderr)
     elapsed_max = max_over_ranks(torch, dist, world, elapsed, dev, backend)
     # algorithmic: CRC input of every frame (header_crc is a prefix: +0)
     bytes_per_launch = w["bytes_per_launch"]
-    parity = parity_sample(torch, w, rank, args.verify, nbad)
+    parity = parity_sample(torch, w, rank, args.verify, nbad) if full else None  # None: not checked by this run
     # Per-rank record (BASELINE configs[3]: "per-GPU and aggregate GiB/s"):
     # each rank's own frames, kernel time by events and wall time between the
     # barriers; gathered on rank 0 (the only other collective of the run).
@@ -742,16 +791,16 @@ def main():
     value = total_bytes / elapsed_max / GIB
     achieved_gbs = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     traffic, traffic_src = read_pmc_traffic(args.config + ("_verify" if args.verify else ""))
-    roof = read_roof(torch, flat, stream) if rank == 0 else None
+    roof = read_roof(torch, flat, stream) if full and rank == 0 else None
 
     host_incl = None
-    if rank == 0 and not args.no_host_inclusive and not args.verify and not args.sort_frames:
+    if full and rank == 0 and not args.no_host_inclusive and not args.verify and not args.sort_frames:
         host_incl = host_inclusive(vc, w)
 
-    windows = verify_windows(torch, vc, flat, dev, stream) if ragged and rank == 0 else None
+    windows = verify_windows(torch, vc, flat, dev, stream) if full and ragged and rank == 0 else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.sort_frames:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.sort_frames:
         visible, effective = effective_cpus()
         threads = args.cpu_threads or min(16, effective)  # the GPU box's CPU share is 16 per GPU
         all_threads = effective  # N = all host cores this process is granted
@@ -820,6 +869,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(elapsed_max / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",

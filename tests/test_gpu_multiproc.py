@@ -35,7 +35,8 @@ def _bench_two_ranks(config: str, *extra: str, ranks: int = 2, timeout: int = 24
     env = dict(os.environ, VAL_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(ranks), "--config", config, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", *extra]
+           "--gpus", str(ranks), "--config", config, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+           *extra]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -81,8 +82,8 @@ def test_bench_eight_ranks_driver_command():
     every rank's parity sample against the oracle."""
     env = dict(os.environ, VAL_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "cfg2", "--with-cfg4-strong",
-           "--no-host-inclusive", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "cfg2", "--full",
+           "--with-cfg4-strong", "--no-host-inclusive", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -116,7 +117,7 @@ def test_bench_cfg4_proxy_at_one_gpu():
     and parity-sampled against the oracle."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--with-cfg4-strong",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--full", "--with-cfg4-strong",
            "--no-host-inclusive", "--no-cpu-baseline", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -136,6 +137,41 @@ def test_bench_cfg4_proxy_at_one_gpu():
     assert rf["bytes_per_launch"] == file_crc_input and rf["read_roof"] and rf["frac_of_read_roof"] > 0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full): the headline fields, none of the extra blocks,
+    and with --dump-outputs the last timed step's CRCs as float64 .npy files,
+    here every one of cfg2's 65,536 frames against the oracle over the same
+    seeded frames generated in this process (so two runs write the same)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from tests import _oracle
+
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "cfg2", "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    bytes_per_step = 65536 * (8 + 8 + 1024)
+    assert abs(line["value"] - bytes_per_step / (line["ms_per_step"] * 1e-3) / 2**30) / line["value"] < 0.01
+    assert line["cpu_baseline"] is None and line["host_inclusive"] is None and line["roofline"]["read_roof"] is None
+    assert "cfg4_strong" not in line and "cfg4_strong_proxy" not in line
+    assert line["config"]["parity_sample_ok"] is None  # the oracle sample belongs to --full
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["crc.npy"]  # cfg2 has no header_crc
+    got = np.load(tmp_path / "out" / "crc.npy")
+    assert got.dtype == np.float64 and got.shape == (65536,)
+    n, payload, explicit, _ = bench.CONFIGS["cfg2"]
+    buf, flen, stride = bench.make_frames(torch, torch.device("cuda:0"), n, payload, explicit, 0, seed=1234)
+    want = _oracle.frames_strided(buf.cpu().numpy().reshape(-1), stride, flen, n)
+    assert np.array_equal(got.astype(np.uint32), want)
+
+
 def test_bench_rccl_process_group_one_rank():
     """The RCCL (nccl backend) code path of bench.py on real hardware: one rank
     under torch.distributed.run with a process group forced on, so the nccl
@@ -145,7 +181,7 @@ def test_bench_rccl_process_group_one_rank():
     env = dict(os.environ, VAL_BENCH_BACKEND="nccl", VAL_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--config", "cfg2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--gpus", "1", "--config", "cfg2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--with-cfg4-strong"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]

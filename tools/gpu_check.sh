@@ -10,7 +10,7 @@ rc=$?
 echo "pytest rc=$rc"; tail -5 $O/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && \
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err && \
-timeout -k 10 600 python bench.py --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err && \
-timeout -k 10 600 python bench.py --config cfg2 --no-cpu-baseline --steps 200 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err && \
+timeout -k 10 600 python bench.py --full --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err && \
+timeout -k 10 600 python bench.py --full --config cfg2 --no-cpu-baseline --steps 200 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
 rc2=$?; echo "check rc=$rc2"; cat $O/bench*.json; exit $rc2

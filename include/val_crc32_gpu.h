@@ -304,6 +304,34 @@ const char *val_gpu_build_flags(void);
 /* ---- introspection for benchmarks ---------------------------------------
  * Lanes per frame the library would pick for a given typical length. */
 uint32_t val_gpu_lanes_per_frame(uint32_t typical_len);
+/* The launches the library would make for one batch of n frames on a device
+ * of `cus` compute units, with the process's current knobs (forced lanes and
+ * prefetch, tail pieces, ragged minimum, the VAL_GPU_* environment). Needs no
+ * device and initialises none. typical_len: flen for strided batches, the
+ * length hint for descriptor batches (0 = unknown or mixed); flen / last_len:
+ * strided batches only. Writes up to two launches (the second is the re-cut
+ * tail of the first) and returns their number. */
+enum {
+    VAL_GPU_KERNEL_RAGGED = 0,    /* binned by length, then one grouped launch */
+    VAL_GPU_KERNEL_SPLIT = 1,     /* one workgroup per frame */
+    VAL_GPU_KERNEL_FRAMES = 2,    /* lanes per frame, persistent waves */
+    VAL_GPU_KERNEL_FRAMES_C0 = 3  /* the same with one-pass loads of round 0 */
+};
+typedef struct val_gpu_launch {
+    uint32_t kernel;        /* VAL_GPU_KERNEL_* */
+    uint32_t lanes;         /* lanes per frame (frames kernels) */
+    int32_t depth;          /* round loop instantiated: 0, 1, 2, 4, -2 or -3 */
+    uint32_t grid;          /* workgroups */
+    uint32_t first, count;  /* frames [first, first + count) */
+    uint32_t k0;            /* split kernel: log2 of the chunk bytes */
+    uint32_t qparts;        /* dynamic-tail queue partitions; 0 = static deal */
+    uint32_t static_rounds; /* with a queue: group rounds dealt before it */
+    uint32_t tail_n;        /* frames after `count` hashed in pieces inside this launch */
+    uint32_t tail_k0;       /* log2 of the piece bytes */
+    uint32_t tail_units;    /* pieces per tail frame */
+} val_gpu_launch_t;
+uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
+                             uint32_t last_len, int want_payload, val_gpu_launch_t out_plan[2]);
 /* Force the lanes-per-frame geometry (1,2,4,...,64) for later calls of this
  * process; 0 restores the automatic choice. Returns VAL_ERR_INVALID_ARG for
  * other values. Results never depend on it; only speed does. */

@@ -1,5 +1,5 @@
 """In-launch tail pieces of the uniform frames kernel (crc_kernels.hpp
-tail_pieces, val_crc32_hip.hip launch_uniform): a uniform batch whose frame
+tail_pieces, launch_plan.hpp tail_piece_k0): a uniform batch whose frame
 groups do not fill the last round of the persistent grid hashes the frames
 past the last full round in 1-4 KiB pieces inside the same launch, each
 piece's register advanced over the bytes after it and folded into its frame
@@ -36,6 +36,13 @@ def _u32(t):
 
 def _waves():
     return torch.cuda.get_device_properties(0).multi_processor_count * 16
+
+
+def _planned_tail(vc, n, typical_len, descriptors=False):
+    """Tail frames the planner hashes inside the launch, at this device's CU count."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    plan = vc.plan_frames(cus, n, typical_len, descriptors=descriptors, flen=0 if descriptors else typical_len)
+    return [l.tail_n for l in plan]
 
 
 def _run_both(vc, fn):
@@ -80,6 +87,7 @@ def test_strided_tail_every_frame(vc, flen, rounds, tail):
 
     on, off, used = _run_both(vc, fn)
     assert used == 1
+    assert _planned_tail(vc, n, flen) == [tail]
     host = buf.cpu().numpy()
     want, want_h = _oracle.frames_strided(host, stride, flen, n, header=True, nthreads=16)
     assert np.array_equal(_u32(on), want)
@@ -122,6 +130,7 @@ def test_descriptor_tail_short_and_empty_frames(vc, hint, rounds, tail):
 
     (on, hon), (off, hoff), used = _run_both(vc, fn)
     assert used == 1
+    assert _planned_tail(vc, n, hint, descriptors=True) == [tail]
     host = buf.cpu().numpy()
     want, want_h = _oracle.frames(host, offs, lens, header=True, nthreads=16)
     assert np.array_equal(_u32(on), want) and np.array_equal(_u32(off), want)

@@ -58,7 +58,7 @@ EXPORTS = (
     "val_gpu_scratch_entries", "val_gpu_set_host_batch_min_bytes", "val_gpu_host_batch_min_bytes",
     "val_gpu_host_batch_min_bytes_for",
     "val_gpu_cpu_batch_count", "val_gpu_set_host_cpu_threads", "val_gpu_host_multi_min_bytes", "val_gpu_host_multi_min_bytes_ex",
-    "val_gpu_set_tail_pieces", "val_gpu_tail_piece_launches",
+    "val_gpu_set_tail_pieces", "val_gpu_tail_piece_launches", "val_gpu_plan_frames",
     "val_batch_attach", "val_batch_flush", "val_batch_get_stats", "val_batch_detach", "val_batch_crc32_provider",
     "val_serialize_handshake", "val_deserialize_handshake", "val_serialize_meta", "val_deserialize_meta",
     "val_serialize_resume_resp", "val_deserialize_resume_resp", "val_serialize_verify_request",
@@ -74,6 +74,21 @@ class ValError(RuntimeError):
     def __init__(self, status: int, where: str, detail: str = ""):
         super().__init__(f"{where} failed: status {status} {detail}".strip())
         self.status = status
+
+
+# val_gpu_launch_t.kernel
+KERNEL_RAGGED, KERNEL_SPLIT, KERNEL_FRAMES, KERNEL_FRAMES_C0 = 0, 1, 2, 3
+
+
+class Launch(ctypes.Structure):
+    """val_gpu_launch_t: one planned launch (include/val_crc32_gpu.h)."""
+    _fields_ = [("kernel", ctypes.c_uint32), ("lanes", ctypes.c_uint32), ("depth", ctypes.c_int32),
+                ("grid", ctypes.c_uint32), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32),
+                ("k0", ctypes.c_uint32), ("qparts", ctypes.c_uint32), ("static_rounds", ctypes.c_uint32),
+                ("tail_n", ctypes.c_uint32), ("tail_k0", ctypes.c_uint32), ("tail_units", ctypes.c_uint32)]
+
+    def astuple(self) -> tuple:
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -162,6 +177,7 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_gpu_host_multi_min_bytes_ex", u64, ctypes.c_int, ctypes.c_int, u64)
     fn("val_gpu_set_tail_pieces", None, ctypes.c_int)
     fn("val_gpu_tail_piece_launches", u64)
+    fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
 
 
 def lib() -> ctypes.CDLL:
@@ -375,6 +391,16 @@ def crc32_shift(state: int, nbytes: int) -> int:
 
 def lanes_per_frame(typical_len: int) -> int:
     return int(lib().val_gpu_lanes_per_frame(typical_len))
+
+
+def plan_frames(cus: int, n: int, typical_len: int, *, descriptors: bool = False, flen: int = 0,
+                last_len: Optional[int] = None, want_payload: bool = False) -> list:
+    """The launches (Launch, at most two) a batch would get on a device of
+    `cus` compute units with the process's current knobs. Needs no GPU."""
+    out = (Launch * 2)()
+    k = lib().val_gpu_plan_frames(cus, n, int(descriptors), typical_len, flen, flen if last_len is None else last_len,
+                                  int(want_payload), out)
+    return [out[i] for i in range(k)]
 
 
 def set_prefetch(on: int) -> None:

@@ -629,7 +629,7 @@ __device__ __forceinline__ void group_pass(const FrameParams &p, uint64_t &f, ui
     fb += step;
 }
 
-// In-launch tail of a uniform launch (launch_uniform). A batch whose frame
+// In-launch tail of a uniform launch (launch_plan.hpp tail_piece_k0). A batch whose frame
 // groups do not fill the last wave-round (131,113 x 64 KiB frames: 8 rounds
 // and 41 frames; a 1 GiB eighth of that file: one round and 6 frames) used to
 // hash those frames in a second small launch after this one: a launch boundary
@@ -660,8 +660,8 @@ __device__ __forceinline__ void tail_desc(const FrameParams &p, uint32_t t, uint
 // Instances that carry the path: 8 and 16 lanes per frame (2-48 KiB and longer
 // frames), the default round depth; in the others its registers made the
 // 32- and 64-lane one-pass kernels spill.
-template <int G, int PF, bool PAY, int BT>
-constexpr bool kTailPieces = (G == 8 || G == 16) && PF == 1 && !PAY && BT == kBlock;
+template <int G, int PF, bool PAY>
+constexpr bool kTailPieces = (G == 8 || G == 16) && PF == 1 && !PAY;
 
 template <int G, int PF, bool C0>
 __device__ __forceinline__ void tail_pieces(const FrameParams &p, int lane, const SliceBases &sb)
@@ -723,11 +723,8 @@ __device__ __forceinline__ void tail_pieces(const FrameParams &p, int lane, cons
     }
 }
 
-// BT: threads per workgroup. 1,024 (16 waves, 128 VGPRs) everywhere, or 512
-// (8 waves, up to 256 VGPRs: deeper rings for short frames; an A/B that lost
-// 10-24%, val_crc32_hip.hip VCRC_W8_PF).
-template <int G, int PF, bool PAY, bool C0 = false, int BT = kBlock>
-__global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
+template <int G, int PF, bool PAY, bool C0 = false>
+__global__ __launch_bounds__(kBlock) void k_frames(const FrameParams p)
 {
     VCRC_STAMP(0);
     VCRC_KARG_EARLY("s"(p.consts), "s"(p.base), "s"(p.off), "s"(p.len), "s"(p.stride), "s"(p.flen), "s"(p.last_len),
@@ -735,10 +732,9 @@ __global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
     constexpr int kGroups = 64 / G;
     const int lane = threadIdx.x & 63;
     const SliceBases sb = slice_bases((uint32_t)(lane & 31) << 2);
-    static_assert(BT == kBlock || !PAY, "payload states need the 1,024-thread pow-map fill");
-    const uint64_t wave = ((uint64_t)blockIdx.x * BT + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * BT) >> 6;
-    LdsImageT<BT> im;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    LdsImage im;
     lds_tables_issue(p.consts, im);
     PowImage pim;
     if constexpr (PAY) lds_pow_issue(p.consts, 0, pim);
@@ -753,7 +749,7 @@ __global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
     // LDS fill and the barrier sit in its hash_frame call, after the frame
     // loads are issued. Peeled, so the LDS image's registers are dead in the
     // loop.
-    const LdsImageT<BT> &cim = im;
+    const LdsImage &cim = im;
     const PowImage &cpim = pim;
     group_pass<G, PF, PAY, C0>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [&cim, &cpim] {
 #ifndef VCRC_NO_LDS_FILL  // diagnostic A/B builds only (wrong CRCs): the prologue's share of small launches
@@ -765,7 +761,7 @@ __global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
     });
     if (!p.qhead) {
         while (fb < p.n) group_pass<G, PF, PAY, C0>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
-        if constexpr (kTailPieces<G, PF, PAY, BT>) {
+        if constexpr (kTailPieces<G, PF, PAY>) {
             if (p.tail_n) tail_pieces<G, PF, C0>(p, lane, sb);
         }
         VCRC_STAMP(2);
@@ -798,14 +794,7 @@ __global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
                     // then holds a reserved long group while others run dry)
         for (;;) {
             uint32_t k = 0;
-#ifdef VCRC_DYN_PRECHECK
-            if (ql == 0) {
-                k = __hip_atomic_load(&p.qhead[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (dyn + (uint64_t)k * kGroups < p.n) k = atomicAdd(&p.qhead[0], 1u);
-            }
-#else
             if (ql == 0) k = atomicAdd(&p.qhead[0], 1u);
-#endif
             k = __builtin_amdgcn_readfirstlane(k);
             const uint64_t gb = dyn + (uint64_t)k * kGroups;
             if (gb >= p.n) break;
@@ -840,7 +829,7 @@ __global__ __launch_bounds__(BT) void k_frames(const FrameParams p)
         od = od_n;
         Ld = Ld_n;
     }
-    if constexpr (kTailPieces<G, PF, PAY, BT>) {
+    if constexpr (kTailPieces<G, PF, PAY>) {
         if (p.tail_n) tail_pieces<G, PF, C0>(p, ql, sb);
     }
     VCRC_STAMP(2);

@@ -21,6 +21,7 @@
 
 #include "cpu_crc32.h"
 #include "crc_kernels.hpp"
+#include "launch_plan.hpp"
 #include "val_crc32_gpu.h"
 #include "val_protocol.h"
 #include "val_wire.h"
@@ -271,38 +272,6 @@ uint32_t forced_lanes()
     return valid_lanes(env_g) ? env_g : 0u;
 }
 
-// Lanes that share one frame (G) in uniform batches, by length: the measured
-// best of the current kernels (profiles/r03_length_sweep.log, strided 3 GB
-// batches): 2 below 1 KiB, 4 below 2 KiB, 8 below 48 KiB,
-// 16 above. G = 8 from 2 KiB gained 3-5% over G = 4 on 2-4 KiB frames and
-// 5% on u4200d (profiles/r03_ab_geom_short.log). The ragged path keeps its
-// length classes (kClassLanes), whose buckets are rounds of their class.
-uint32_t lanes_per_frame(uint32_t len)
-{
-    const uint32_t f = forced_lanes();
-    if (f) return f;
-    return len < 1024u ? 2u : len < 2048u ? 4u : len < 49152u ? 8u : 16u;
-}
-
-// G for a uniform batch of n frames of len bytes: the class's G, doubled while
-// the batch would leave more than half of the machine's waves idle (a small
-// window spreads each frame over more lanes, so its serial chain is shorter),
-// up to one wave per frame and at most one 64-B unit per lane per round. The
-// doubling only acts on batches of fewer groups than half the machine's waves
-// (one pass of the grid); large batches keep the class's measured G. Capping
-// it at 16 cost small windows of long frames 1.5-2.5x (256 x 64 KiB: 103 ->
-// 41 us per call; 256 x 16 KiB: 34 -> 20 us; profiles/r02_ab_lanes_cap.log).
-uint32_t lanes_for_batch(const Ctx &c, uint32_t len, uint64_t n)
-{
-    uint32_t G = lanes_per_frame(len);
-    if (forced_lanes()) return G;
-    const uint64_t waves = (uint64_t)c.cus * kWavesPerBlock;
-    const uint64_t units = len ? (len + kUnit - 1) / kUnit : 1u;
-    const uint32_t cap = 64u;
-    while (G < cap && 2u * G <= units && (n + 64 / G - 1) / (64 / G) * 2u <= waves) G *= 2;
-    return G;
-}
-
 // 0, 1, 2, 4: copy-and-refill depths; -2, -3: in-place rings (G = 2 and 4 only)
 bool valid_prefetch(int d) { return d == 0 || d == 1 || d == 2 || d == 4 || d == -2 || d == -3; }
 
@@ -315,99 +284,19 @@ int forced_prefetch()
     return valid_prefetch(env_p) ? env_p : -1;
 }
 
-// Rounds kept in flight ahead of the one being hashed: 1 unless forced
-// (launch_uniform_g turns the automatic 1 into the in-place rings at G = 2, 4).
-// Measured on MI355X (profiles/r01_small_batches.log): issuing every round up
-// front (2 or 4 deep) lost 5-15% even on one-pass batches such as cfg2, since
-// the whole batch's requests then land before any wave can start hashing.
-int prefetch_depth()
-{
-    const int forced = forced_prefetch();
-    return forced != -1 ? forced : 1;
-}
-
 StreamScratch &scratch_for(Ctx &c, hipStream_t s);
 template <typename K, typename... Args>
 hipError_t launch_tracked(StreamScratch *x, K kernel, dim3 grid, dim3 block, hipStream_t s, Args... args);
-
-// one_pass: every wave hashes at most one frame group (windows, cfg2): round
-// 0's units by dword loads (k_frames C0; crc_kernels.hpp load_unit0).
-// x: the stream scratch the launch uses (the dynamic-tail queue), else null.
-template <int G>
-hipError_t launch_uniform_g(int pf, dim3 grid, hipStream_t s, const FrameParams &p, bool one_pass, StreamScratch *x,
-                             uint32_t len)
-{
-    const dim3 b(kBlock);
-    if (p.out_pay) return launch_tracked(x, k_frames<G, 1, true>, grid, b, s, p);  // payload states: default depth only
-// A/B builds: one-pass launches' round loop. Rings measured no better on
-// cfg2 (two deep +0.6% back to back, -3.7% single launch; three deep -7%) and
-// equal on 64-4,096-frame windows (profiles/r04_ab_ring_prefetch_one_pass.log).
-#ifndef VCRC_C0_PF
-#define VCRC_C0_PF 1
-#endif
-    if (pf == 1 && one_pass) return launch_tracked(x, k_frames<G, (G == 2 || G == 4) ? VCRC_C0_PF : 1, false, true>, grid, b, s, p);
-    // Multi-pass short frames hash each round in its registers and refill them
-    // in place (a ring of -pf rounds, crc_kernels.hpp hash_frame BURST):
-    // profiles/r04_ab_ring_prefetch.log, same box against the copy-and-refill
-    // PF = 1 loop: G = 2 three deep u600d +4.2% (two deep +1.8%); G = 4 two
-    // deep u1100d +1.5-1.8%, s1100 0%, u2000d -0.3 to -0.6% (three deep -0.7 to
-    // -3%), so 4 lanes take the ring below 1,600 B (R <= 7) only.
-#ifndef VCRC_RING_G2
-#define VCRC_RING_G2 -3
-#endif
-#ifndef VCRC_RING_G4
-#define VCRC_RING_G4 -2
-#endif
-    if (pf == 1 && forced_prefetch() == -1) pf = G == 2 ? VCRC_RING_G2 : (G == 4 && len < 1600u) ? VCRC_RING_G4 : 1;
-    if constexpr (G == 2 || G == 4) {
-        if (pf == -3) return launch_tracked(x, k_frames<G, -3, false>, grid, b, s, p);
-        if (pf == -2) return launch_tracked(x, k_frames<G, -2, false>, grid, b, s, p);
-    }
-    switch (pf) {
-    case 0: return launch_tracked(x, k_frames<G, 0, false>, grid, b, s, p);
-    case 2: return launch_tracked(x, k_frames<G, 2, false>, grid, b, s, p);
-    case 4: return launch_tracked(x, k_frames<G, 4, false>, grid, b, s, p);
-    default: return launch_tracked(x, k_frames<G, 1, false>, grid, b, s, p);
-    }
-}
-
 val_status_t arena_acquire(Arena &a, size_t bytes, hipStream_t s, uint8_t **out);
 
-// Dynamic tail of long uniform launches (k_frames): VAL_GPU_DYNAMIC_TAIL=0/1.
-// A launch takes it when it is long enough for the queue to pay: 8 or 16
-// lanes per frame from 1.45 MiB of frames per wave (about 6 GB at 4,096
-// waves), 2 or 4 lanes from 8 group rounds. Shorter launches measured faster
-// static, once the exits were counted per workgroup (same box, back to back,
-// profiles/r06_ab_dyn_tail_rules.log): 64 KiB frames 4 / 5 rounds -2.5 /
-// -0.6% with the queue, 6 / 7 rounds +0.5 / +1.0%; 16,400-B frames 6 / 8
-// rounds -3.7 / -1.6%, 12 / 16 rounds +0.5 / +1.6%; 4,200-B frames (8 lanes,
-// 34 KiB groups) 4 / 8 / 12 rounds -8 / -5 / -3.6%; 1,100-B and 2,000-B frames
-// at 4 rounds -5% and -3.9%, 600-B and 1,100-B frames at 8 rounds +3.6% and
-// +3.2%.
-#ifndef VCRC_DYN_MIN_WAVE_BYTES
-#define VCRC_DYN_MIN_WAVE_BYTES 1520000u
-#endif
-#ifndef VCRC_DYN_MIN_ROUNDS_SHORT
-#define VCRC_DYN_MIN_ROUNDS_SHORT 8
-#endif
-#ifndef VCRC_DYN_TAIL_DEFAULT
-#define VCRC_DYN_TAIL_DEFAULT 1
-#endif
+// Dynamic tail of long uniform launches (launch_plan.hpp): VAL_GPU_DYNAMIC_TAIL=0/1.
 bool dyn_tail_enabled()
 {
-    static const bool on = getenv("VAL_GPU_DYNAMIC_TAIL") ? atoi(getenv("VAL_GPU_DYNAMIC_TAIL")) != 0
-                                                         : VCRC_DYN_TAIL_DEFAULT != 0;
+    static const bool on = !(getenv("VAL_GPU_DYNAMIC_TAIL") && atoi(getenv("VAL_GPU_DYNAMIC_TAIL")) == 0);
     return on;
 }
 
-// Small batches of long frames go to k_frames_split (one workgroup per frame,
-// its chunks hashed by 16 waves at once) when that takes fewer memory rounds
-// per wave than one wave per frame: ceil(n / CUs) passes of about three
-// round-times each (a chunk round, the fold, the next frame's start) against
-// ceil(units / 64) rounds. Measured (profiles/r02_ab_split.log): 256 x 64 KiB
-// 41 -> 18 us per call, 256 x 8 KiB 21.5 -> 16 us, equal at 1024 x 64 KiB,
-// slower at 2048 x 64 KiB and 512 x 16 KiB (the rule keeps those off it).
-// Payload states and forced geometries keep the frames kernels.
+// Small batches of long frames on k_frames_split (launch_plan.hpp use_split):
 // VAL_GPU_SPLIT=0 disables it.
 bool split_enabled()
 {
@@ -418,148 +307,30 @@ bool split_enabled()
     return on;
 }
 
-bool use_split(const Ctx &c, const FrameParams &p, uint32_t len)
+// The k_frames instantiation of a planned launch (lanes, depth, one-pass
+// loads, payload states). x: the stream scratch the launch uses (the
+// dynamic-tail queue, the tail accumulators), else null.
+template <int G>
+hipError_t launch_k_frames(const Launch &l, StreamScratch *x, hipStream_t s, const FrameParams &p)
 {
-    if (!split_enabled() || p.out_pay || forced_lanes() || forced_prefetch() != -1 || len < 8192u) return false;
-    const uint64_t waves = (uint64_t)c.cus * kWavesPerBlock;
-    if ((uint64_t)p.n * 2u > waves) return false;
-    const uint64_t rounds = ((uint64_t)len / kUnit + 1u + 63u) / 64u;  // at one wave per frame
-    const uint64_t passes = ((uint64_t)p.n + c.cus - 1u) / (uint64_t)c.cus;
-    return passes * 3u <= rounds;
+    const dim3 grid(l.grid), b(kBlock);
+    if (p.out_pay) return launch_tracked(x, k_frames<G, 1, true>, grid, b, s, p);
+    if (l.kernel == kKernelFramesC0) return launch_tracked(x, k_frames<G, 1, false, true>, grid, b, s, p);
+    if constexpr (G == 2 || G == 4) {
+        if (l.depth == -3) return launch_tracked(x, k_frames<G, -3, false>, grid, b, s, p);
+        if (l.depth == -2) return launch_tracked(x, k_frames<G, -2, false>, grid, b, s, p);
+    }
+    switch (l.depth) {
+    case 0: return launch_tracked(x, k_frames<G, 0, false>, grid, b, s, p);
+    case 1: return launch_tracked(x, k_frames<G, 1, false>, grid, b, s, p);
+    case 2: return launch_tracked(x, k_frames<G, 2, false>, grid, b, s, p);
+    case 4: return launch_tracked(x, k_frames<G, 4, false>, grid, b, s, p);
+    default: return hipErrorInvalidValue;
+    }
 }
 
-val_status_t launch_split(const Ctx &c, FrameParams &p, uint32_t len, hipStream_t s)
-{
-    p.consts = c.d_consts;
-    // W = 2^k0 >= 1 KiB with a typical frame in at most 16 chunks (one group)
-    uint32_t k0 = 10;
-    while (((uint64_t)kWavesPerBlock << k0) < (uint64_t)len && k0 < 31) k0++;
-    const dim3 grid((unsigned)std::min<uint64_t>(p.n, (uint64_t)c.cus));
-    hipLaunchKernelGGL(k_frames_split, grid, dim3(kBlock), 0, s, p, k0);
-    VCRC_HIP(hipGetLastError(), "k_frames_split launch");
-    return VAL_OK;
-}
-
-val_status_t launch_uniform_one(const Ctx &c, FrameParams &p, uint32_t G, uint32_t len, hipStream_t s)
-{
-    p.consts = c.d_consts;
-// A/B builds: multi-pass G = 2/4 batches on 512-thread workgroups (8 waves
-// per CU, up to 256 VGPRs: 185 used) with a ring of -VCRC_W8_PF rounds, so a
-// 1,100-B group's rounds are all in flight at entry. 10-24% slower than 16
-// waves with the 2/3-rings (u1100d -23%, s1100 -18%, u600d -11%, u2000d -10%;
-// profiles/r04_ab_eight_waves_deep_ring.log): the table chains need the waves.
-#ifndef VCRC_W8_PF
-#define VCRC_W8_PF 0
-#endif
-    const bool w8 = VCRC_W8_PF != 0 && (G == 2 || G == 4) && !p.out_pay && forced_prefetch() == -1 &&
-                    (uint64_t)p.n > (uint64_t)c.cus * 16u * (64u / G);  // more than one pass at 16 waves per CU
-    const uint32_t wpb = w8 ? 8u : (uint32_t)kWavesPerBlock;
-    const uint64_t groups_per_block = (uint64_t)wpb * (64 / G);
-    uint64_t blocks = (p.n + groups_per_block - 1) / groups_per_block;
-    blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)c.cus));  // persistent, 1 per CU (LDS)
-    const dim3 grid((unsigned)blocks);
-    const int pf = prefetch_depth();
-    // Dynamic tail for long launches: the last half of the group rounds come
-    // from a queue (k_frames). Groups of >= 128 KiB (strided) or 192 KiB
-    // (descriptors) pull from one word: 4,096 waves over 128 KiB groups is
-    // about 48 dequeues/us at 6 TB/s, under the ~88/us one word serves, and
-    // one word evens the end out better than partitions (cfg3 -1.5%, cfg4 -3.7%
-    // with 64). Groups under 128 KiB pull from 64 partitions: descriptor groups
-    // from 16 KiB (round 2: u4200d +4%, u1100d +6%; with one word they lost up to 2x),
-    // strided ones from 32 KiB (s4200 +3%; s1100's 17.6 KiB groups -3%);
-    // descriptor groups of 128-192 KiB stay static below 16 rounds (u16400d
-    // -1% either way: profiles/r02_ab_dynparts.log) and take one word above.
-    // Which launches are long enough for any queue: VCRC_DYN_MIN_WAVE_BYTES above.
-    const uint64_t rounds = ((uint64_t)p.n + 64 / G - 1) / (64 / G) / (blocks * wpb);
-    p.qhead = nullptr;
-    const uint64_t group_bytes = (uint64_t)(64 / G) * len;
-#ifndef VCRC_DYN_MIN_GROUP  // A/B builds may override: one-word minimum group bytes, strided / descriptor batches
-#define VCRC_DYN_MIN_GROUP (128u << 10)
-#endif
-#ifndef VCRC_DYN_MIN_GROUP_DESC
-#define VCRC_DYN_MIN_GROUP_DESC (192u << 10)
-#endif
-#ifndef VCRC_DYN_MIN_GROUP_PARTS  // partitioned queue minimum group bytes, strided / descriptor batches
-#define VCRC_DYN_MIN_GROUP_PARTS (32u << 10)
-#endif
-#ifndef VCRC_DYN_MIN_GROUP_PARTS_DESC
-#define VCRC_DYN_MIN_GROUP_PARTS_DESC (16u << 10)
-#endif
-    // Descriptor groups of 128-192 KiB take the one-word queue only from 16
-    // rounds on: cfg3's layout through descriptors (32 rounds) +3.0%, 3 GB of
-    // 16,400-B frames (6 rounds) -2.8% with it (profiles/r06_ab_desc_dyn_tail.log).
-#ifndef VCRC_DYN_DESC_LONG_ROUNDS
-#define VCRC_DYN_DESC_LONG_ROUNDS 16
-#endif
-    const bool one_word = group_bytes >= (p.off ? (rounds >= VCRC_DYN_DESC_LONG_ROUNDS ? VCRC_DYN_MIN_GROUP
-                                                                                       : VCRC_DYN_MIN_GROUP_DESC)
-                                                : VCRC_DYN_MIN_GROUP);
-    const bool parts =
-        group_bytes >= (p.off ? VCRC_DYN_MIN_GROUP_PARTS_DESC : VCRC_DYN_MIN_GROUP_PARTS) && group_bytes < VCRC_DYN_MIN_GROUP;
-    // the queue's scratch may be dropped by scratch_for (another stream's call)
-    // unless the lock is held until the kernel is launched
-    Ctx &cm = const_cast<Ctx &>(c);
-    std::lock_guard<std::recursive_mutex> lk(cm.mu);
-    StreamScratch *used = nullptr;
-    if (p.tail_n) {  // in-launch tail pieces (launch_uniform): a zeroed accumulator pair per tail frame
-        used = &scratch_for(cm, s);
-        Arena &a = used->tail;
-        uint8_t *q = nullptr;
-        const size_t bytes = (size_t)p.tail_n * 8u;
-        val_status_t st = arena_acquire(a, bytes, s, &q);
-        if (st != VAL_OK) return st;
-        if (!a.counts_zero) VCRC_HIP(hipMemsetAsync(q, 0, a.cap, s), "hipMemsetAsync(tail)");
-        a.counts_zero = false;  // set again once the launch is queued (its last pieces re-zero the pairs)
-        p.tail_acc = reinterpret_cast<uint32_t *>(q);
-    }
-    const bool long_enough = G >= 8 ? rounds * group_bytes >= (uint64_t)VCRC_DYN_MIN_WAVE_BYTES
-                                    : rounds >= VCRC_DYN_MIN_ROUNDS_SHORT;
-    if (dyn_tail_enabled() && long_enough && (one_word || parts)) {
-        if (!used) used = &scratch_for(cm, s);
-        Arena &a = used->queue;
-        uint8_t *q = nullptr;
-        val_status_t st = arena_acquire(a, kDynQueueBytes, s, &q);
-        if (st != VAL_OK) return st;
-        if (!a.counts_zero) VCRC_HIP(hipMemsetAsync(q, 0, kDynQueueBytes, s), "hipMemsetAsync(queue)");
-        a.counts_zero = true;  // the last wave out re-zeroes it
-        p.qhead = reinterpret_cast<uint32_t *>(q);
-        p.qparts = one_word ? 1u : kDynParts;
-#ifndef VCRC_DYN_DIV
-#define VCRC_DYN_DIV 2
-#endif
-        p.static_rounds = (uint32_t)(VCRC_DYN_DIV == 1 ? 1u : rounds - std::max<uint64_t>(1, rounds / VCRC_DYN_DIV));
-    }
-    const bool one_pass = ((uint64_t)p.n + 64 / G - 1) / (64 / G) <= (uint64_t)grid.x * wpb;
-    hipError_t e = hipSuccess;
-    if (w8) {
-        if (G == 2) e = launch_tracked(used, k_frames<2, (VCRC_W8_PF < 0 ? VCRC_W8_PF : -2), false, false, 512>, grid, dim3(512), s, p);
-        else e = launch_tracked(used, k_frames<4, (VCRC_W8_PF < 0 ? VCRC_W8_PF : -2), false, false, 512>, grid, dim3(512), s, p);
-        VCRC_HIP(e, "k_frames launch");
-        return VAL_OK;
-    }
-    switch (G) {
-    case 1: e = launch_uniform_g<1>(pf, grid, s, p, one_pass, used, len); break;
-    case 2: e = launch_uniform_g<2>(pf, grid, s, p, one_pass, used, len); break;
-    case 4: e = launch_uniform_g<4>(pf, grid, s, p, one_pass, used, len); break;
-    case 8: e = launch_uniform_g<8>(pf, grid, s, p, one_pass, used, len); break;
-    case 16: e = launch_uniform_g<16>(pf, grid, s, p, one_pass, used, len); break;
-    case 32: e = launch_uniform_g<32>(pf, grid, s, p, one_pass, used, len); break;
-    case 64: e = launch_uniform_g<64>(pf, grid, s, p, one_pass, used, len); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    if (p.tail_n && e == hipSuccess) used->tail.counts_zero = true;
-    VCRC_HIP(e, "k_frames launch");
-    return VAL_OK;
-}
-
-// In-launch tail pieces (crc_kernels.hpp tail_pieces): the frames past the
-// last full wave-round, cut into pieces of W = 2^k0 bytes and hashed by the
-// oldest waves as one extra frame group each, instead of a second launch.
-// W = 1 KiB (one round at 16 lanes: the extra work per wave stays under what
-// the oldest waves gain on the youngest), doubled while the piece groups
-// outnumber the waves. Kernels with G = 8 or 16 at the default depth carry
-// the path; frames of at least 8 KiB use it. VAL_GPU_TAIL_PIECES=0 or
-// val_gpu_set_tail_pieces(0) keeps the second launch (A/B).
+// In-launch tail pieces (launch_plan.hpp tail_piece_k0): VAL_GPU_TAIL_PIECES=0
+// or val_gpu_set_tail_pieces(0) keeps the second launch (A/B).
 std::atomic<int> g_tail_pieces{-1};  // -1: VAL_GPU_TAIL_PIECES (unset = on); 0 / 1: val_gpu_set_tail_pieces
 std::atomic<uint64_t> g_tail_piece_launches{0};
 bool tail_pieces_enabled()
@@ -570,70 +341,61 @@ bool tail_pieces_enabled()
     return on;
 }
 
-// log2 of the piece bytes for this tail, or 0 when the path does not apply.
-uint32_t tail_piece_k0(const Ctx &c, const FrameParams &p, uint32_t G, uint32_t len, uint64_t n_tail)
+val_status_t launch_split(const Ctx &c, FrameParams &p, const Launch &l, hipStream_t s)
 {
-    if (!tail_pieces_enabled() || p.out_pay || (G != 8 && G != 16) || len < 8192u || n_tail == 0 ||
-        forced_prefetch() != -1)
-        return 0;
-    for (uint32_t k0 = kPieceK0Min; k0 <= 16; k0++) {
-        const uint64_t units = n_tail * (((uint64_t)len + (1u << k0) - 1) >> k0);
-        if ((units + 64 / G - 1) / (64 / G) <= (uint64_t)c.cus * kWavesPerBlock) return k0;
-    }
-    return 0;
+    p.consts = c.d_consts;
+    hipLaunchKernelGGL(k_frames_split, dim3(l.grid), dim3(kBlock), 0, s, p, l.k0);
+    VCRC_HIP(hipGetLastError(), "k_frames_split launch");
+    return VAL_OK;
 }
 
-// Persistent waves take whole frame groups, so a launch lasts
-// ceil(groups / waves) group-times: 131,113 frames of 64 KiB at G = 16 are
-// 8.002 wave-rounds, the last one 99.8% idle. The frames of a partial last
-// round are re-cut with more lanes per frame (up to 64) into a second launch
-// on the same stream, so the tail costs about G / G_tail of a group-time.
-val_status_t launch_uniform(const Ctx &c, FrameParams &p, uint32_t G, uint32_t len, hipStream_t s)
+// One planned k_frames launch: the tail accumulators and the queue the plan
+// asks for, then the kernel.
+val_status_t launch_uniform_one(Ctx &c, FrameParams &p, const Launch &l, hipStream_t s)
 {
-    const uint64_t per = 64 / G, groups = (p.n + per - 1) / per;
-    const uint64_t waves = (uint64_t)c.cus * kWavesPerBlock;
-    const uint64_t full = groups / waves;
-    uint32_t Gt = G;
-    const uint64_t n_main = full * waves * per, n_tail = p.n - std::min<uint64_t>(p.n, n_main);
-    if (full > 0 && n_tail > 0)
-        while (Gt < 64 && (n_tail + 64 / (2 * Gt) - 1) / (64 / (2 * Gt)) <= waves) Gt *= 2;
-    if (Gt == G) return launch_uniform_one(c, p, G, len, s);
-    if (const uint32_t k0 = tail_piece_k0(c, p, G, len, n_tail)) {
-        FrameParams m = p;
-        m.n = (uint32_t)n_main;
-        m.tail_n = (uint32_t)n_tail;
-        m.tail_k0 = k0;
-        m.tail_units = (uint32_t)(((uint64_t)len + (1u << k0) - 1) >> k0);
-        if (!p.off) {
-            m.last_len = p.flen;  // frame n_main - 1 is a full one
-            m.tail_last_len = p.last_len;
-        }
-        const val_status_t st = launch_uniform_one(c, m, G, len, s);
-        if (st == VAL_OK) g_tail_piece_launches.fetch_add(1, std::memory_order_relaxed);
-        return st;
+    p.consts = c.d_consts;
+    p.qhead = nullptr;
+    // the queue's scratch may be dropped by scratch_for (another stream's call)
+    // unless the lock is held until the kernel is launched
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    StreamScratch *used = nullptr;
+    if (p.tail_n) {  // in-launch tail pieces: a zeroed accumulator pair per tail frame
+        used = &scratch_for(c, s);
+        Arena &a = used->tail;
+        uint8_t *q = nullptr;
+        const size_t bytes = (size_t)p.tail_n * 8u;
+        val_status_t st = arena_acquire(a, bytes, s, &q);
+        if (st != VAL_OK) return st;
+        if (!a.counts_zero) VCRC_HIP(hipMemsetAsync(q, 0, a.cap, s), "hipMemsetAsync(tail)");
+        a.counts_zero = false;  // set again once the launch is queued (its last pieces re-zero the pairs)
+        p.tail_acc = reinterpret_cast<uint32_t *>(q);
     }
-    FrameParams m = p, t = p;
-    m.n = (uint32_t)n_main;
-    t.n = (uint32_t)n_tail;
-    if (p.off) {
-        t.off = p.off + n_main;
-        t.len = p.len + n_main;
-    } else {
-        m.last_len = p.flen;
-        t.base = p.base + n_main * p.stride;
+    if (l.qparts) {
+        if (!used) used = &scratch_for(c, s);
+        Arena &a = used->queue;
+        uint8_t *q = nullptr;
+        val_status_t st = arena_acquire(a, kDynQueueBytes, s, &q);
+        if (st != VAL_OK) return st;
+        if (!a.counts_zero) VCRC_HIP(hipMemsetAsync(q, 0, kDynQueueBytes, s), "hipMemsetAsync(queue)");
+        a.counts_zero = true;  // the last wave out re-zeroes it
+        p.qhead = reinterpret_cast<uint32_t *>(q);
+        p.qparts = l.qparts;
+        p.static_rounds = l.static_rounds;
     }
-    t.seed0 = p.seed_rest;  // frame 0 is in the main part
-    if (p.out_crc) t.out_crc = p.out_crc + n_main;
-    if (p.out_hdr) t.out_hdr = p.out_hdr + n_main;
-    if (p.out_ok) t.out_ok = p.out_ok + n_main;
-    if (p.out_pay) t.out_pay = p.out_pay + n_main;
-    val_status_t st = launch_uniform_one(c, m, G, len, s);
-    if (st != VAL_OK) return st;
-    // a tail of a few long frames (cfg4: 41 x 64 KiB after 8 full rounds) is a
-    // small batch of its own: one workgroup per frame when that is faster
-    const uint32_t tl = t.off ? len : std::max(t.flen, t.last_len);
-    if (use_split(c, t, tl)) return launch_split(c, t, tl, s);
-    return launch_uniform_one(c, t, Gt, tl, s);
+    hipError_t e = hipSuccess;
+    switch (l.lanes) {
+    case 1: e = launch_k_frames<1>(l, used, s, p); break;
+    case 2: e = launch_k_frames<2>(l, used, s, p); break;
+    case 4: e = launch_k_frames<4>(l, used, s, p); break;
+    case 8: e = launch_k_frames<8>(l, used, s, p); break;
+    case 16: e = launch_k_frames<16>(l, used, s, p); break;
+    case 32: e = launch_k_frames<32>(l, used, s, p); break;
+    case 64: e = launch_k_frames<64>(l, used, s, p); break;
+    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
+    }
+    if (p.tail_n && e == hipSuccess) used->tail.counts_zero = true;
+    VCRC_HIP(e, "k_frames launch");
+    return VAL_OK;
 }
 
 void arena_free(Arena &a);
@@ -750,7 +512,7 @@ void arena_free(Arena &a)
 
 // Ragged descriptor batch: counting-sort by length on the device, then one
 // grouped launch planned by bytes per length class (no host synchronisation).
-val_status_t launch_ragged(Ctx &c, FrameParams &p, hipStream_t s)
+val_status_t launch_ragged(Ctx &c, FrameParams &p, const Launch &l, hipStream_t s)
 {
     const uint32_t n = p.n;
     const uint32_t nbin = std::max(1u, std::min(1024u, (n + 2047u) / 2048u));
@@ -784,20 +546,11 @@ val_status_t launch_ragged(Ctx &c, FrameParams &p, hipStream_t s)
         p.plan = ctab;
         p.heads = heads;
         p.bin_counts = gcount;
-        // persistent: enough waves for the items, at most one workgroup per CU
-        const uint64_t max_items = (n + 3u) / 4u + kClasses;  // every class packs >= 4 frames per item
-        const unsigned blocks = (unsigned)std::max<uint64_t>(
-            1, std::min<uint64_t>((uint64_t)c.cus, (max_items + kWavesPerBlock - 1) / kWavesPerBlock));
         // the ragged kernel is the last of the three on the stream to use the scratch
-        if (p.out_pay) e = launch_tracked(&ss, k_frames_ragged<1, true>, dim3(blocks), dim3(kBlock), s, p);
-        else if (forced_prefetch() == 0) e = launch_tracked(&ss, k_frames_ragged<0, false>, dim3(blocks), dim3(kBlock), s, p);
-// A/B builds: the ragged kernel's round loop (1 = copy and refill, -2 / -3 =
-// rings). The rings lost 9-11% on cfg5 and the class-2 mix and 2-3% on 600 and
-// 1,100-B frames through the ragged path (profiles/r04_ab_ring_prefetch_ragged.log).
-#ifndef VCRC_RAGGED_PF
-#define VCRC_RAGGED_PF 1
-#endif
-        else e = launch_tracked(&ss, k_frames_ragged<VCRC_RAGGED_PF, false>, dim3(blocks), dim3(kBlock), s, p);
+        const dim3 grid(l.grid);
+        if (p.out_pay) e = launch_tracked(&ss, k_frames_ragged<1, true>, grid, dim3(kBlock), s, p);
+        else if (l.depth == 0) e = launch_tracked(&ss, k_frames_ragged<0, false>, grid, dim3(kBlock), s, p);
+        else e = launch_tracked(&ss, k_frames_ragged<1, false>, grid, dim3(kBlock), s, p);
         a.counts_zero = e == hipSuccess;
     }
     if (e != hipSuccess) return fail(VAL_ERR_IO, "ragged frames launch", e);
@@ -835,14 +588,60 @@ uint32_t ragged_min_frames()
     return env >= 0 ? (uint32_t)std::min<int64_t>(env, UINT32_MAX) : kRaggedMinFrames;
 }
 
+// The process's run-time knobs, as the planner takes them.
+PlanKnobs plan_knobs()
+{
+    return PlanKnobs{forced_lanes(), forced_prefetch(), dyn_tail_enabled(), split_enabled(), tail_pieces_enabled(),
+                     ragged_min_frames()};
+}
+
+// Frames [l.first, l.first + l.count) of batch p as a batch of their own, with
+// the launch's in-launch tail frames after them.
+FrameParams slice_frames(const FrameParams &p, const Launch &l)
+{
+    FrameParams q = p;
+    q.n = l.count;
+    if (l.first) {
+        if (p.off) {
+            q.off = p.off + l.first;
+            q.len = p.len + l.first;
+        } else {
+            q.base = p.base + (uint64_t)l.first * p.stride;
+        }
+        q.seed0 = p.seed_rest;  // frame 0 is in the first part
+        if (p.out_crc) q.out_crc = p.out_crc + l.first;
+        if (p.out_hdr) q.out_hdr = p.out_hdr + l.first;
+        if (p.out_ok) q.out_ok = p.out_ok + l.first;
+        if (p.out_pay) q.out_pay = p.out_pay + l.first;
+    }
+    if (!p.off && l.first + l.count < p.n) q.last_len = p.flen;  // the part's last frame is a full one
+    if (l.tail_n) {
+        q.tail_n = l.tail_n;
+        q.tail_k0 = l.tail_k0;
+        q.tail_units = l.tail_units;
+        if (!p.off) q.tail_last_len = p.last_len;
+    }
+    return q;
+}
+
+// Plans the batch (launch_plan.hpp) and executes the plan.
 val_status_t launch_frames(Ctx &c, FrameParams &p, uint32_t typical_len, hipStream_t s)
 {
-    if (p.n == 0) return VAL_OK;
-    if (p.off && typical_len == 0 && !forced_lanes() && p.n >= ragged_min_frames()) return launch_ragged(c, p, s);
-    const uint32_t len = typical_len ? typical_len : 16384u;
-    const uint32_t longest = !p.off ? std::max(p.flen, p.last_len) : len;
-    if (use_split(c, p, longest)) return launch_split(c, p, longest, s);
-    return launch_uniform(c, p, lanes_for_batch(c, len, p.n), len, s);
+    const LaunchPlan plan =
+        plan_frames((uint32_t)c.cus, p.n, typical_len, p.off != nullptr, p.flen, p.last_len, p.out_pay != nullptr, plan_knobs());
+    for (uint32_t i = 0; i < plan.count; i++) {
+        const Launch &l = plan.launch[i];
+        val_status_t st = VAL_OK;
+        if (l.kernel == kKernelRagged) {
+            st = launch_ragged(c, p, l, s);
+        } else {
+            FrameParams q = slice_frames(p, l);
+            st = l.kernel == kKernelSplit ? launch_split(c, q, l, s) : launch_uniform_one(c, q, l, s);
+        }
+        if (st != VAL_OK) return st;
+        if (l.tail_n) g_tail_piece_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    return VAL_OK;
 }
 
 // NULL selects the HIP default (null) stream, as in every HIP API.
@@ -1935,7 +1734,7 @@ const char *val_gpu_last_error(void) { return t_err.c_str(); }
 
 const char *val_gpu_build_flags(void)
 {
-    // every compile-time switch of the sources, diagnostic or A/B, that is set
+    // the diagnostic compile-time switches that are set (tests/test_build.py)
     static const char flags[] = ""
 #ifdef VCRC_DIAG_BUILD
                                 " VCRC_DIAG_BUILD"
@@ -2086,7 +1885,19 @@ uint64_t val_gpu_cpu_fallback_count(void) { return g_cpu_fallbacks.load(std::mem
 
 void val_gpu_set_cpu_fallback(int enable) { g_cpu_fallback_on.store(enable < 0 ? -1 : (enable ? 1 : 0)); }
 
-uint32_t val_gpu_lanes_per_frame(uint32_t typical_len) { return lanes_per_frame(typical_len); }
+uint32_t val_gpu_lanes_per_frame(uint32_t typical_len)
+{
+    return Planner{0, false, false, 0, 0, plan_knobs()}.lanes_per_frame(typical_len);
+}
+
+uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
+                             uint32_t last_len, int want_payload, val_gpu_launch_t out_plan[2])
+{
+    const LaunchPlan plan =
+        plan_frames(cus, n, typical_len, descriptors != 0, flen, last_len, want_payload != 0, plan_knobs());
+    for (uint32_t i = 0; out_plan && i < plan.count; i++) out_plan[i] = plan.launch[i];
+    return plan.count;
+}
 
 val_status_t val_gpu_set_lanes_per_frame(uint32_t lanes)
 {
@@ -2171,9 +1982,11 @@ uint32_t val_gpu_crc32_provider(uint32_t seed, const void *buf, size_t len)
     return scalar_state("val_gpu_crc32_provider", seed, buf, len) ^ 0xFFFFFFFFu;
 }
 
-val_status_t val_crc32_frames_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len, uint64_t stride,
-                                  uint32_t flen, uint32_t n, uint32_t len_hint, uint32_t *d_crc, uint32_t *d_hdr,
-                                  void *stream)
+// The device-resident frame calls: argument checks, the batch's FrameParams
+// and the launch. verify = 0: CRCs only (d_ok, d_nbad and d_pay unused).
+static val_status_t frames_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len, uint64_t stride,
+                               uint32_t flen, uint32_t n, uint32_t len_hint, uint32_t verify, uint8_t *d_ok,
+                               uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr, uint32_t *d_pay, void *stream)
 {
     t_err.clear();
     if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
@@ -2194,36 +2007,25 @@ val_status_t val_crc32_frames_dev(const uint8_t *d_base, const uint64_t *d_off, 
     p.xorout = 0xFFFFFFFFu;
     p.out_crc = d_crc;
     p.out_hdr = d_hdr;
+    p.verify = verify;
+    p.out_ok = d_ok;
+    p.nbad = d_nbad;
+    p.out_pay = d_pay;
     return launch_frames(*c, p, d_off ? len_hint : flen, pick_stream(stream));
+}
+
+val_status_t val_crc32_frames_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len, uint64_t stride,
+                                  uint32_t flen, uint32_t n, uint32_t len_hint, uint32_t *d_crc, uint32_t *d_hdr,
+                                  void *stream)
+{
+    return frames_dev(d_base, d_off, d_len, stride, flen, n, len_hint, 0, nullptr, nullptr, d_crc, d_hdr, nullptr, stream);
 }
 
 val_status_t val_crc32_verify_frames_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
                                          uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint, uint8_t *d_ok,
                                          uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr, void *stream)
 {
-    t_err.clear();
-    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
-    if (!d_base && n) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
-    DeviceScope ds;
-    Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_base, &c);
-    if (st != VAL_OK) return st;
-    FrameParams p{};
-    p.base = d_base;
-    p.off = d_off;
-    p.len = d_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
-    p.out_crc = d_crc;
-    p.out_hdr = d_hdr;
-    p.verify = 1;
-    p.out_ok = d_ok;
-    p.nbad = d_nbad;
-    return launch_frames(*c, p, d_off ? len_hint : flen, pick_stream(stream));
+    return frames_dev(d_base, d_off, d_len, stride, flen, n, len_hint, 1, d_ok, d_nbad, d_crc, d_hdr, nullptr, stream);
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,
@@ -2284,30 +2086,7 @@ val_status_t val_crc32_verify_frames_ex_dev(const uint8_t *d_base, const uint64_
                                             uint8_t *d_ok, uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr,
                                             uint32_t *d_pay, void *stream)
 {
-    t_err.clear();
-    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
-    if (!d_base && n) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
-    DeviceScope ds;
-    Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_base, &c);
-    if (st != VAL_OK) return st;
-    FrameParams p{};
-    p.base = d_base;
-    p.off = d_off;
-    p.len = d_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
-    p.out_crc = d_crc;
-    p.out_hdr = d_hdr;
-    p.verify = 1;
-    p.out_ok = d_ok;
-    p.nbad = d_nbad;
-    p.out_pay = d_pay;
-    return launch_frames(*c, p, d_off ? len_hint : flen, pick_stream(stream));
+    return frames_dev(d_base, d_off, d_len, stride, flen, n, len_hint, 1, d_ok, d_nbad, d_crc, d_hdr, d_pay, stream);
 }
 
 val_status_t val_crc32_verify_frames_ex_host(const uint8_t *base, uint64_t base_len, const uint64_t *off,

@@ -144,6 +144,46 @@ val_status_t val_crc32_verify_frames_ex_dev(const uint8_t *d_base, const uint64_
                                             uint8_t *d_ok, uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr,
                                             uint32_t *d_pay, void *stream);
 
+/* TX framing on the device: val_frame_data_batch + the trailer CRC +
+ * val_frame_put_trailers (include/val_wire.h) in one launch, async on
+ * `stream` (the per-packet work of reference src/val_core.c:733-834 for a
+ * whole window). All pointers are device pointers. Frame i is laid out byte
+ * for byte as the host framer does: the 8-byte header (VAL_PKT_DATA, flags
+ * VAL_DATA_OFFSET_PRESENT iff d_include_offset[i] != 0, NULL = every frame;
+ * content_len LE16; type_data 0), the LE64 d_file_off[i] when explicit, payload
+ * bytes [d_pay_off[i], d_pay_off[i] + d_pay_len[i]) of d_payload, and the LE32
+ * CRC-32 of those 8 + content bytes.
+ * Placement: d_frame_off[i] when given (val_frame_data_layout computes the
+ * host framer's back-to-back stream once on the host), else frame i at
+ * i * out_stride (a ring of slots).
+ * Outputs (n entries each, any may be NULL; they feed
+ * val_crc32_verify_frames_*_dev directly): d_crc_len[i] = 8 + content,
+ * d_crc[i] = the trailer value, d_hdr[i] = header_crc as above.
+ * Rejected frames: where the host framer refuses the whole batch, a device
+ * call has no lengths to look at without a synchronise, so it rejects frame by
+ * frame and counts. A frame is rejected when its content exceeds 65535 bytes,
+ * in slot mode when 12 + content > out_stride, and when d_pay_len[i] > 0 while
+ * d_payload or d_pay_off is NULL: no byte of d_out is written for it,
+ * d_crc_len[i] = d_crc[i] = d_hdr[i] = 0, and *d_nrejected (device u32,
+ * nullable) is INCREMENTED (zero it first).
+ * Only the 12 + content wire bytes of accepted frames are written; every other
+ * byte of d_out keeps its value. Only aligned dwords that overlap a frame's
+ * payload range are read.
+ * d_payload / d_pay_off may be NULL only if every d_pay_len[i] is 0 (the
+ * caller's promise: it cannot be checked without a synchronise). d_out must
+ * not overlap d_payload and frames must not overlap each other.
+ * len_hint: typical CRC-input length (picks the lanes per frame, speed only;
+ * 0 = unknown; val_gpu_set_lanes_per_frame forces it).
+ * n == 0 returns VAL_OK without a launch; NULL d_out, d_pay_len or d_file_off,
+ * or NULL d_frame_off with out_stride < 12, return VAL_ERR_INVALID_ARG before
+ * any launch (val_gpu_last_error says which). The call runs on the stream's
+ * device (else the device d_out lives on) and keeps no library scratch. */
+val_status_t val_frame_data_batch_dev(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint32_t *d_pay_len,
+                                      const uint64_t *d_file_off, const uint8_t *d_include_offset, uint32_t n,
+                                      uint8_t *d_out, const uint64_t *d_frame_off, uint64_t out_stride,
+                                      uint32_t len_hint, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
+                                      uint32_t *d_nrejected, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8

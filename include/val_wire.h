@@ -115,6 +115,17 @@ val_status_t val_frame_data_batch(const uint8_t *payload, const uint64_t *pay_of
                                   const uint64_t *file_off, const uint8_t *include_offset, uint32_t n, uint8_t *out,
                                   size_t out_cap, uint64_t *frame_off, uint32_t *crc_len, size_t *out_used);
 
+/*
+ * Where val_frame_data_batch would put each frame, without writing one (host
+ * only, no GPU): frame_off[i], crc_len[i] (either may be NULL) and *total,
+ * the stream's length. The framer's own positions come from this function.
+ * Upload frame_off to place val_frame_data_batch_dev's frames back to back
+ * (include/val_crc32_gpu.h). A content_len above 65535 returns
+ * VAL_ERR_INVALID_ARG, as the framer does.
+ */
+val_status_t val_frame_data_layout(const uint32_t *pay_len, const uint8_t *include_offset, uint32_t n,
+                                   uint64_t *frame_off, uint32_t *crc_len, uint64_t *total);
+
 /* Write LE32 trailers crc[i] after each frame's CRC input. */
 void val_frame_put_trailers(uint8_t *stream, const uint64_t *frame_off, const uint32_t *crc_len, const uint32_t *crc,
                             uint32_t n);

@@ -64,6 +64,7 @@ EXPORTS = (
     "val_serialize_resume_resp", "val_deserialize_resume_resp", "val_serialize_verify_request",
     "val_deserialize_verify_request", "val_serialize_verify_response", "val_deserialize_verify_response",
     "val_serialize_error_payload", "val_deserialize_error_payload",
+    "val_frame_data_batch_dev", "val_frame_data_layout",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -177,6 +178,8 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_gpu_host_multi_min_bytes_ex", u64, ctypes.c_int, ctypes.c_int, u64)
     fn("val_gpu_set_tail_pieces", None, ctypes.c_int)
     fn("val_gpu_tail_piece_launches", u64)
+    fn("val_frame_data_batch_dev", i32, _vp, _vp, _vp, _vp, _vp, u32, _vp, _vp, u64, u32, _vp, _vp, _vp, _vp, _vp)
+    fn("val_frame_data_layout", i32, _vp, _vp, u32, _vp, _vp, ctypes.POINTER(u64))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
 
 

@@ -22,6 +22,7 @@
 #include "cpu_crc32.h"
 #include "crc_kernels.hpp"
 #include "launch_plan.hpp"
+#include "pack_kernel.hpp"
 #include "val_crc32_gpu.h"
 #include "val_protocol.h"
 #include "val_wire.h"
@@ -1642,6 +1643,22 @@ void ctx_free(Ctx &c)
     if (c.stream) (void)hipStreamDestroy(c.stream);
 }
 
+// Device framer (pack_kernel.hpp): one k_pack launch on the caller's stream.
+// Lanes per frame: forced (val_gpu_set_lanes_per_frame), else from len_hint as
+// the hash kernels choose them; without a hint, the geometry of MTU-sized
+// frames, which is correct for every length; a batch too small to fill the
+// grid doubles them until it does. A persistent grid of at most one workgroup
+// per CU; the kernel uses no scratch.
+template <int G>
+hipError_t launch_k_pack(const PackParams &p, uint32_t cus, hipStream_t s)
+{
+    const uint64_t groups = ((uint64_t)p.n + (64 / G) - 1) / (64 / G);
+    const uint64_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, std::max(cus, 1u));
+    hipLaunchKernelGGL(k_pack<G>, dim3(grid), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
 }  // namespace vcrc
 
 using namespace vcrc;
@@ -2026,6 +2043,59 @@ val_status_t val_crc32_verify_frames_dev(const uint8_t *d_base, const uint64_t *
                                          uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr, void *stream)
 {
     return frames_dev(d_base, d_off, d_len, stride, flen, n, len_hint, 1, d_ok, d_nbad, d_crc, d_hdr, nullptr, stream);
+}
+
+val_status_t val_frame_data_batch_dev(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint32_t *d_pay_len,
+                                      const uint64_t *d_file_off, const uint8_t *d_include_offset, uint32_t n,
+                                      uint8_t *d_out, const uint64_t *d_frame_off, uint64_t out_stride,
+                                      uint32_t len_hint, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
+                                      uint32_t *d_nrejected, void *stream)
+{
+    t_err.clear();
+    if (n == 0) return VAL_OK;
+    if (!d_out || !d_pay_len || !d_file_off) return fail(VAL_ERR_INVALID_ARG, "out, pay_len or file_off is NULL");
+    if (!d_frame_off && out_stride < VAL_WIRE_HEADER_SIZE + VAL_WIRE_TRAILER_SIZE)
+        return fail(VAL_ERR_INVALID_ARG, "out_stride below 12 without frame_off");
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    val_status_t st = cur_dev(stream, d_out, &c);
+    if (st != VAL_OK) return st;
+    PackParams p{};
+    p.payload = d_payload;
+    p.pay_off = d_pay_off;
+    p.pay_len = d_pay_len;
+    p.file_off = d_file_off;
+    p.include_offset = d_include_offset;
+    p.n = n;
+    p.out = d_out;
+    p.frame_off = d_frame_off;
+    p.stride = out_stride;
+    p.out_len = d_crc_len;
+    p.out_crc = d_crc;
+    p.out_hdr = d_hdr;
+    p.nrejected = d_nrejected;
+    p.consts = c->d_consts;
+    uint32_t lanes = forced_lanes();
+    if (!lanes) {
+        lanes = val_gpu_lanes_per_frame(len_hint ? len_hint : 1100u);
+        // A batch that leaves workgroups of the grid empty doubles its lanes until it fills them
+        // (65,536 frames at 2 lanes are 128 of 256 workgroups).
+        while (lanes < 64u && (uint64_t)n * lanes * 2u <= (uint64_t)std::max(c->cus, 1) * kBlock) lanes *= 2u;
+    }
+    const hipStream_t s = pick_stream(stream);
+    hipError_t e = hipErrorInvalidValue;
+    switch (lanes) {
+    case 1: e = launch_k_pack<1>(p, (uint32_t)c->cus, s); break;
+    case 2: e = launch_k_pack<2>(p, (uint32_t)c->cus, s); break;
+    case 4: e = launch_k_pack<4>(p, (uint32_t)c->cus, s); break;
+    case 8: e = launch_k_pack<8>(p, (uint32_t)c->cus, s); break;
+    case 16: e = launch_k_pack<16>(p, (uint32_t)c->cus, s); break;
+    case 32: e = launch_k_pack<32>(p, (uint32_t)c->cus, s); break;
+    case 64: e = launch_k_pack<64>(p, (uint32_t)c->cus, s); break;
+    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
+    }
+    VCRC_HIP(e, "k_pack launch");
+    return VAL_OK;
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

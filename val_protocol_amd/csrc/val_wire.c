@@ -187,6 +187,30 @@ void val_deserialize_error_payload(const uint8_t *wire_data, val_error_payload_t
 }
 
 /* ---- batch framing ------------------------------------------------------ */
+val_status_t val_frame_data_layout(const uint32_t *pay_len, const uint8_t *include_offset, uint32_t n,
+                                   uint64_t *frame_off, uint32_t *crc_len, uint64_t *total)
+{
+    if (total)
+        *total = 0;
+    if (n && !pay_len)
+        return VAL_ERR_INVALID_ARG;
+    uint64_t pos = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const int explicit_off = include_offset ? (include_offset[i] != 0) : 1;
+        const uint64_t content = (uint64_t)pay_len[i] + (explicit_off ? 8u : 0u);
+        if (content > VAL_WIRE_MAX_CONTENT)
+            return VAL_ERR_INVALID_ARG; /* the reference would wrap content_len here */
+        if (frame_off)
+            frame_off[i] = pos;
+        if (crc_len)
+            crc_len[i] = (uint32_t)(VAL_WIRE_HEADER_SIZE + content);
+        pos += VAL_WIRE_HEADER_SIZE + content + VAL_WIRE_TRAILER_SIZE;
+    }
+    if (total)
+        *total = pos;
+    return VAL_OK;
+}
+
 val_status_t val_frame_data_batch(const uint8_t *payload, const uint64_t *pay_off, const uint32_t *pay_len,
                                   const uint64_t *file_off, const uint8_t *include_offset, uint32_t n, uint8_t *out,
                                   size_t out_cap, uint64_t *frame_off, uint32_t *crc_len, size_t *out_used)
@@ -195,18 +219,22 @@ val_status_t val_frame_data_batch(const uint8_t *payload, const uint64_t *pay_of
         *out_used = 0;
     if (n && (!pay_len || !file_off || !out || !frame_off || !crc_len))
         return VAL_ERR_INVALID_ARG;
-    size_t pos = 0;
+    /* Every frame's position comes from val_frame_data_layout, one frame at a
+     * time: the frames before a refused one are laid out as they always were. */
+    uint64_t pos = 0;
     for (uint32_t i = 0; i < n; i++) {
-        const int explicit_off = include_offset ? (include_offset[i] != 0) : 1;
-        const uint64_t content = (uint64_t)pay_len[i] + (explicit_off ? 8u : 0u);
-        if (content > VAL_WIRE_MAX_CONTENT)
-            return VAL_ERR_INVALID_ARG; /* the reference would wrap content_len here */
+        const uint8_t *inc = include_offset ? include_offset + i : NULL;
+        uint64_t at = 0, wire = 0;
+        uint32_t clen = 0;
+        if (val_frame_data_layout(pay_len + i, inc, 1, &at, &clen, &wire) != VAL_OK)
+            return VAL_ERR_INVALID_ARG;
         if (pay_len[i] && (!payload || !pay_off))
             return VAL_ERR_INVALID_ARG;
-        const size_t wire = VAL_WIRE_HEADER_SIZE + (size_t)content + VAL_WIRE_TRAILER_SIZE;
-        if (wire > out_cap - pos)
+        if (wire > (uint64_t)out_cap - pos)
             return VAL_ERR_INVALID_ARG;
-        uint8_t *f = out + pos;
+        const uint32_t content = clen - VAL_WIRE_HEADER_SIZE;
+        const int explicit_off = content != pay_len[i];
+        uint8_t *f = out + pos + at;
         val_serialize_frame_header((uint8_t)VAL_PKT_DATA, explicit_off ? (uint8_t)VAL_DATA_OFFSET_PRESENT : 0u,
                                    (uint16_t)content, 0u, f);
         uint8_t *c = f + VAL_WIRE_HEADER_SIZE;
@@ -216,13 +244,13 @@ val_status_t val_frame_data_batch(const uint8_t *payload, const uint64_t *pay_of
         }
         if (pay_len[i])
             memcpy(c, payload + pay_off[i], pay_len[i]);
-        memset(f + VAL_WIRE_HEADER_SIZE + content, 0, VAL_WIRE_TRAILER_SIZE);
-        frame_off[i] = pos;
-        crc_len[i] = (uint32_t)(VAL_WIRE_HEADER_SIZE + content);
+        memset(f + clen, 0, VAL_WIRE_TRAILER_SIZE);
+        frame_off[i] = pos + at;
+        crc_len[i] = clen;
         pos += wire;
     }
     if (out_used)
-        *out_used = pos;
+        *out_used = (size_t)pos;
     return VAL_OK;
 }
 

@@ -64,6 +64,61 @@ def put_trailers(stream: np.ndarray, frame_off, crc_len, crc) -> None:
                                  crc.size)
 
 
+def data_layout(pay_len, include_offset=None):
+    """Where build_data_batch puts each frame (val_frame_data_layout; host only):
+    returns (frame_off uint64, crc_len uint32, total bytes)."""
+    pay_len = np.ascontiguousarray(pay_len, dtype=np.uint32)
+    n = pay_len.size
+    inc = None
+    if include_offset is not None:
+        inc = np.ascontiguousarray(include_offset, dtype=np.uint8)
+    frame_off = np.zeros(n, dtype=np.uint64)
+    crc_len = np.zeros(n, dtype=np.uint32)
+    total = ctypes.c_uint64(0)
+    st = lib().val_frame_data_layout(pay_len.ctypes.data, inc.ctypes.data if inc is not None else None, n,
+                                     frame_off.ctypes.data, crc_len.ctypes.data, ctypes.byref(total))
+    _check(st, "val_frame_data_layout")
+    return frame_off, crc_len, int(total.value)
+
+
+def build_data_batch_dev(payload, pay_off, pay_len, file_off, include_offset=None, *, out, frame_off=None,
+                         out_stride: int = 0, len_hint: int = 0, out_crc=None, out_hdr=None, nrejected=None,
+                         stream=None):
+    """Frame a window on the GPU, trailers included (val_frame_data_batch_dev):
+    one launch on torch's current stream (or ``stream``), returns at once.
+
+    All arguments are GPU tensors: ``payload`` and ``out`` uint8, ``pay_off``,
+    ``file_off`` and ``frame_off`` int64 (uint64 bit patterns), ``pay_len``
+    int32, ``include_offset`` uint8 (None: every frame explicit). Frames go to
+    ``frame_off`` (data_layout gives the back-to-back stream) or, without it,
+    to slots of ``out_stride`` bytes. Returns (crc_len, crc, nrejected): int32
+    tensors of n, n and 1 entries; ``out_hdr`` (int32, n) receives header_crc.
+    ``nrejected`` (int32[1], the caller's, already on the stream) is
+    incremented instead of a fresh zeroed counter.
+    """
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    n = int(pay_len.numel())
+    dev = out.device
+    crc_len = torch.empty(n, dtype=torch.int32, device=dev)
+    if out_crc is None:
+        out_crc = torch.empty(n, dtype=torch.int32, device=dev)
+    nrej = nrejected
+    if nrej is None:
+        nrej = torch.zeros(1, dtype=torch.int32, device=dev)
+        if stream is not None:  # the counter's zero fill is ordered before the launch
+            nrej.record_stream(stream)
+            stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_data_batch_dev(_dptr(payload), _dptr(pay_off), _dptr(pay_len), _dptr(file_off),
+                                        _dptr(include_offset), n, _dptr(out), _dptr(frame_off), out_stride, len_hint,
+                                        _dptr(crc_len), _dptr(out_crc), _dptr(out_hdr), _dptr(nrej),
+                                        _stream_ptr(stream))
+    _check(st, "val_frame_data_batch_dev")
+    return crc_len, out_crc, nrej
+
+
 def scan_frames(stream: np.ndarray, mtu: int, max_frames: int = 1 << 30):
     """Returns (status, frame_off, crc_len, consumed)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -105,5 +160,5 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     return out
 
 
-__all__ = ["serialize_header", "deserialize_header", "build_data_batch", "put_trailers", "scan_frames", "payload_lens",
+__all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout", "put_trailers", "scan_frames", "payload_lens",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

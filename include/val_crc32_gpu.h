@@ -184,6 +184,60 @@ val_status_t val_frame_data_batch_dev(const uint8_t *d_payload, const uint64_t *
                                       uint32_t len_hint, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
                                       uint32_t *d_nrejected, void *stream);
 
+/* RX delivery on the device, the counterpart of val_frame_data_batch_dev: a
+ * window of received frames in HBM goes in, and the call leaves on the device
+ * what the reference's receive loop would have produced for it (the trailer
+ * check of src/val_core.c:963-993, then the ordering decision, the fwrite and
+ * the rolling CRC of src/val_receiver.c:871-895): the payloads at their place
+ * in the GPU-resident file d_file, *d_written, the rolling *d_file_state and
+ * the per-frame verdicts. Async on `stream`, no host synchronisation. All
+ * pointers are device pointers; frames are described as for
+ * val_crc32_verify_frames_ex_dev (d_base, d_off, d_len, stride, flen, n,
+ * len_hint; descriptor lengths are the caller's and may be 0 .. 2^32-1, not
+ * only what the LE16 content_len can say).
+ * It is a short pipeline on the stream, not one launch (DESIGN.md section
+ * 4.9): a payload may be written only after its own CRC matched and the
+ * verdicts of all earlier frames are known.
+ *   1. verify: the launches of val_crc32_verify_frames_ex_dev. d_ok[i]
+ *      (nullable) and *d_nbad (nullable, INCREMENTED) as there.
+ *   2. order: the rule of val_frame_accept (val_wire.h) over the header facts
+ *      of val_frame_data_offsets / val_frame_payload_lens, with
+ *      W = *d_written. Frame i is accepted iff its trailer matched, it is a
+ *      DATA frame, its effective offset (the explicit LE64, or W when implied)
+ *      equals W, and W + pay_len <= file_cap (no 64-bit wrap-around). An
+ *      accepted frame is delivered at W and advances W by pay_len; every other
+ *      frame (corrupt, control, duplicate, gap, too short for its offset) is
+ *      skipped and later frames are still judged one by one. d_accept[i]
+ *      (nullable) = 1 / 0; *d_naccepted and *d_noverflow (device u32,
+ *      nullable) are INCREMENTED by the frames accepted and by the frames
+ *      refused by the capacity test alone (zero them first). *d_written = W.
+ *      *d_file_state (raw register, nullable) becomes
+ *      shift(state, pay_len) ^ pay_state over the accepted frames in order,
+ *      i.e. val_crc32_fold_payload_states_at's result.
+ *   3. scatter: accepted payload i is copied to d_file + its offset. Bytes of
+ *      d_file outside the accepted ranges keep their values (no
+ *      read-modify-write of a neighbouring dword); only aligned dwords of
+ *      d_base that overlap an accepted payload are read for the copy.
+ * d_file must hold file_cap bytes and must not overlap d_base.
+ * d_work: the caller's workspace of at least val_frame_unpack_work_bytes(n)
+ * bytes, 8-byte aligned (verdicts, payload states, destinations, header
+ * facts); its contents after the call are unspecified. The call keeps no
+ * library scratch beyond what the verify stage uses per stream.
+ * Two calls on one stream chain: the second continues from the first's
+ * *d_written and *d_file_state.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when d_off and d_len are not both set or both NULL, d_work is NULL or
+ * misaligned, work_bytes is below val_frame_unpack_work_bytes(n), and, with
+ * n > 0, when d_file, d_written or d_base is NULL. Otherwise n == 0 returns
+ * VAL_OK, launches nothing and changes nothing. The call runs on the stream's
+ * device (else the device d_file lives on). */
+uint64_t val_frame_unpack_work_bytes(uint32_t n);
+val_status_t val_frame_unpack_batch_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                        uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint, uint8_t *d_file,
+                                        uint64_t file_cap, uint64_t *d_written, uint32_t *d_file_state, uint8_t *d_ok,
+                                        uint32_t *d_nbad, uint8_t *d_accept, uint32_t *d_naccepted,
+                                        uint32_t *d_noverflow, void *d_work, uint64_t work_bytes, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8

@@ -164,6 +164,29 @@ void val_frame_payload_lens(const uint8_t *stream, const uint64_t *frame_off, co
 void val_frame_data_offsets(const uint8_t *stream, const uint64_t *frame_off, const uint32_t *crc_len, uint32_t n,
                             uint64_t *file_off);
 
+/*
+ * The receiver's ordering rule over a scanned batch (reference
+ * src/val_receiver.c:871-895), host only: which frames are delivered into the
+ * file and where. file_off[] from val_frame_data_offsets, pay_len[] from
+ * val_frame_payload_lens, ok[] the trailer verdicts (NULL = all good). With
+ * W = *written, frame after frame: a frame is accepted iff ok[i] != 0, it is a
+ * DATA frame (file_off[i] != VAL_FRAME_OFFSET_NOT_DATA), its effective offset
+ * (file_off[i], or W for VAL_FRAME_OFFSET_IMPLIED) equals W, and
+ * W + pay_len[i] <= file_cap (judged without 64-bit wrap-around). An accepted
+ * frame gets dst_off[i] = W and advances W by pay_len[i]; every other frame
+ * gets dst_off[i] = VAL_FRAME_NOT_ACCEPTED and leaves W alone (duplicates,
+ * gaps, corrupt and control frames; later frames are still judged one by
+ * one). A frame refused by the capacity test alone is counted in *n_overflow.
+ * *written = W on return; *n_accepted / *n_overflow (nullable) are set, not
+ * incremented; dst_off may be NULL. With file_cap = UINT64_MAX the accepted
+ * frames are exactly those val_crc32_fold_payload_states_at folds. It states
+ * the rule val_frame_unpack_batch_dev (val_crc32_gpu.h) applies on the device.
+ */
+#define VAL_FRAME_NOT_ACCEPTED UINT64_MAX
+void val_frame_accept(const uint64_t *file_off, const uint32_t *pay_len, const uint8_t *ok, uint32_t n,
+                      uint64_t file_cap, uint64_t *written, uint64_t *dst_off, uint32_t *n_accepted,
+                      uint32_t *n_overflow);
+
 #ifdef __cplusplus
 }
 #endif

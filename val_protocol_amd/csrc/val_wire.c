@@ -326,3 +326,39 @@ void val_frame_data_offsets(const uint8_t *stream, const uint64_t *frame_off, co
             file_off[i] = val_get_le64(f + VAL_WIRE_HEADER_SIZE);
     }
 }
+
+void val_frame_accept(const uint64_t *file_off, const uint32_t *pay_len, const uint8_t *ok, uint32_t n,
+                      uint64_t file_cap, uint64_t *written, uint64_t *dst_off, uint32_t *n_accepted,
+                      uint32_t *n_overflow)
+{
+    uint32_t accepted = 0, overflow = 0;
+    if (n_accepted)
+        *n_accepted = 0;
+    if (n_overflow)
+        *n_overflow = 0;
+    if (!written || (n && (!file_off || !pay_len)))
+        return;
+    uint64_t w = *written;
+    for (uint32_t i = 0; i < n; i++) {
+        if (dst_off)
+            dst_off[i] = VAL_FRAME_NOT_ACCEPTED;
+        if ((ok && !ok[i]) || file_off[i] == VAL_FRAME_OFFSET_NOT_DATA)
+            continue;
+        const uint64_t eff = file_off[i] == VAL_FRAME_OFFSET_IMPLIED ? w : file_off[i];
+        if (eff != w)
+            continue; /* duplicate or gap */
+        if (w > file_cap || (uint64_t)pay_len[i] > file_cap - w) { /* w + pay_len > file_cap, without the wrap */
+            overflow++;
+            continue;
+        }
+        if (dst_off)
+            dst_off[i] = w;
+        w += pay_len[i];
+        accepted++;
+    }
+    *written = w;
+    if (n_accepted)
+        *n_accepted = accepted;
+    if (n_overflow)
+        *n_overflow = overflow;
+}

@@ -119,6 +119,88 @@ def build_data_batch_dev(payload, pay_off, pay_len, file_off, include_offset=Non
     return crc_len, out_crc, nrej
 
 
+NOT_ACCEPTED = (1 << 64) - 1  # VAL_FRAME_NOT_ACCEPTED (val_wire.h)
+
+
+def frame_accept(file_off, pay_len, written: int, file_cap: int = (1 << 64) - 1, ok=None):
+    """The receiver's ordering rule over a scanned batch (val_frame_accept; host
+    only): ``file_off`` from data_offsets, ``pay_len`` from payload_lens, ``ok``
+    the trailer verdicts (None: all good). Returns (dst_off uint64 with
+    NOT_ACCEPTED for skipped frames, written, n_accepted, n_overflow)."""
+    file_off = np.ascontiguousarray(file_off, dtype=np.uint64)
+    pay_len = np.ascontiguousarray(pay_len, dtype=np.uint32)
+    n = pay_len.size
+    okp = None
+    if ok is not None:
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        okp = ok.ctypes.data
+    dst = np.zeros(n, dtype=np.uint64)
+    w = ctypes.c_uint64(written)
+    nacc, novf = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().val_frame_accept(file_off.ctypes.data, pay_len.ctypes.data, okp, n, file_cap, ctypes.byref(w),
+                           dst.ctypes.data, ctypes.byref(nacc), ctypes.byref(novf))
+    return dst, int(w.value), int(nacc.value), int(novf.value)
+
+
+def unpack_work_bytes(n: int) -> int:
+    """Workspace bytes unpack_data_batch_dev needs for n frames."""
+    return int(lib().val_frame_unpack_work_bytes(n))
+
+
+def unpack_data_batch_dev(base, *, file, written, off=None, length=None, stride: int = 0, flen: int = 0, n=None,
+                          len_hint: int = 0, file_cap=None, file_state=None, out_ok=None, nbad=None, accept=None,
+                          naccepted=None, noverflow=None, work=None, stream=None):
+    """Verify a window of received frames and deliver the accepted payloads
+    into a GPU-resident file (val_frame_unpack_batch_dev): a few launches on
+    torch's current stream (or ``stream``), returns at once.
+
+    All tensors live on the GPU. ``base`` uint8 and frames as in
+    crc.verify_frames (``off`` int64 / ``length`` int32, or strided with
+    ``stride``/``flen``/``n``). ``file`` uint8 (``file_cap``: its capacity,
+    default its size); ``written`` int64[1] and ``file_state`` int32[1] (raw
+    register, optional) are read and updated in place, so calls chain.
+    ``out_ok`` / ``accept`` uint8[n] and the counters ``nbad``, ``naccepted``,
+    ``noverflow`` (int32[1], incremented) are allocated (counters zeroed) when
+    not given; ``work`` is the workspace (uint8, unpack_work_bytes(n)).
+    Returns (ok, accept, nbad, naccepted, noverflow).
+    """
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    if n is None:
+        n = int(off.numel()) if off is not None else 0
+    dev = file.device
+    if file_cap is None:
+        file_cap = int(file.numel())
+    fresh = []
+    if out_ok is None:
+        out_ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        fresh.append(out_ok)
+    if accept is None:
+        accept = torch.empty(n, dtype=torch.uint8, device=dev)
+        fresh.append(accept)
+    if work is None:
+        work = torch.empty(max(unpack_work_bytes(n), 16), dtype=torch.uint8, device=dev)
+        fresh.append(work)
+    counters = []
+    for c in (nbad, naccepted, noverflow):
+        if c is None:
+            c = torch.zeros(1, dtype=torch.int32, device=dev)
+            fresh.append(c)
+        counters.append(c)
+    if stream is not None and fresh:  # allocations and zero fills are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_unpack_batch_dev(_dptr(base), _dptr(off), _dptr(length), stride, flen, n, len_hint,
+                                          _dptr(file), file_cap, _dptr(written), _dptr(file_state), _dptr(out_ok),
+                                          _dptr(counters[0]), _dptr(accept), _dptr(counters[1]), _dptr(counters[2]),
+                                          _dptr(work), int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_frame_unpack_batch_dev")
+    return out_ok, accept, counters[0], counters[1], counters[2]
+
+
 def scan_frames(stream: np.ndarray, mtu: int, max_frames: int = 1 << 30):
     """Returns (status, frame_off, crc_len, consumed)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -160,5 +242,6 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     return out
 
 
-__all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout", "put_trailers", "scan_frames", "payload_lens",
+__all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout",
+           "unpack_data_batch_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "payload_lens",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

@@ -238,6 +238,60 @@ val_status_t val_frame_unpack_batch_dev(const uint8_t *d_base, const uint64_t *d
                                         uint32_t *d_nbad, uint8_t *d_accept, uint32_t *d_naccepted,
                                         uint32_t *d_noverflow, void *d_work, uint64_t work_bytes, void *stream);
 
+/* RX delivery for many receivers at once: one window that holds frames of
+ * n_files transfers, delivered in one asynchronous call. For every file it
+ * leaves what val_frame_unpack_batch_dev, called on that file's frames alone,
+ * would have left, bit for bit: the file bytes, written, the state, ok[],
+ * accept[] and the counters (the ordering decision of
+ * src/val_receiver.c:871-895 once per file). The pipeline is that call's with
+ * one launch per stage: one verify over all n frames, one parse, one order
+ * launch whose workgroups each take whole files (the rule is sequential only
+ * within a file), one scatter over all n frames. All pointers are device
+ * pointers; nothing is synchronised.
+ * Frames are described as for val_frame_unpack_batch_dev (d_base, d_off,
+ * d_len, stride, flen, n, len_hint; any length 0 .. 2^32-1; len_hint 0 = the
+ * ragged verify path). The caller groups the DESCRIPTORS by file: file s owns
+ * frames [d_first[s], d_first[s+1]) of the n (d_first has n_files + 1
+ * entries); the frames themselves may lie anywhere in d_base, in any order.
+ * Per file s, with W = d_written[s] and cap = d_file_cap[s], the rule of
+ * val_frame_accept runs over its frames in index order; accepted payloads are
+ * copied to d_file_ptr[s] + W (d_file_ptr[s] is the device address of a file
+ * of at least d_file_cap[s] bytes); d_written[s] is updated;
+ * d_file_state[s] (raw registers, array nullable) folds
+ * shift(state, pay_len) ^ pay_state over the file's accepted frames;
+ * d_naccepted[s], d_noverflow[s] and d_file_nbad[s] (frames of file s whose
+ * trailer did not match) are INCREMENTED (arrays nullable; zero them first).
+ * d_ok[i] and d_accept[i] (n entries, nullable) and *d_nbad (whole batch,
+ * nullable, INCREMENTED) are as in the single-file call. Only bytes of
+ * accepted ranges are written, per file, with no read-modify-write of a
+ * neighbouring dword.
+ * The segment boundaries live on the device and cannot be checked without a
+ * synchronise, so they are made safe rather than trusted: file s owns
+ * [min(d_first[s], n), min(max(d_first[s+1], d_first[s]), n)); a decreasing
+ * pair is an empty file, which changes nothing of that file's entries. A frame
+ * that no file owns is still verified (d_ok[i], *d_nbad), gets
+ * d_accept[i] = 0 and is never delivered. Overlapping segments are the
+ * caller's error: a frame owned twice may land in either file, and d_accept[i]
+ * may speak for either; it never lands outside that file's capacity and no
+ * out-of-bounds access happens. Files must not overlap each other or d_base.
+ * d_work: val_frame_unpack_work_bytes(n) bytes, 8-byte aligned, as in the
+ * single-file call; there is no per-file workspace and no library scratch
+ * beyond what the verify stage keeps per stream. Two calls on one stream
+ * chain, file by file.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when d_off and d_len are not both set or both NULL, d_work is NULL or
+ * misaligned, work_bytes is below val_frame_unpack_work_bytes(n), and, with
+ * n > 0 and n_files > 0, when d_first, d_file_ptr, d_file_cap, d_written or
+ * d_base is NULL. Otherwise n == 0 or n_files == 0 returns VAL_OK, launches
+ * nothing and changes nothing. The call runs on the stream's device (else the
+ * device d_written lives on). */
+val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                        uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint, uint32_t n_files,
+                                        const uint32_t *d_first, const uint64_t *d_file_ptr, const uint64_t *d_file_cap,
+                                        uint64_t *d_written, uint32_t *d_file_state, uint32_t *d_naccepted,
+                                        uint32_t *d_noverflow, uint32_t *d_file_nbad, uint8_t *d_ok, uint32_t *d_nbad,
+                                        uint8_t *d_accept, void *d_work, uint64_t work_bytes, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8

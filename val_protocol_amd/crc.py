@@ -66,6 +66,7 @@ EXPORTS = (
     "val_serialize_error_payload", "val_deserialize_error_payload",
     "val_frame_data_batch_dev", "val_frame_data_layout",
     "val_frame_unpack_work_bytes", "val_frame_unpack_batch_dev", "val_frame_accept",
+    "val_frame_unpack_files_dev",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -184,6 +185,8 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_frame_unpack_work_bytes", u64, u32)
     fn("val_frame_unpack_batch_dev", i32, _vp, _vp, _vp, u64, u32, u32, u32, _vp, u64, _vp, _vp, _vp, _vp, _vp, _vp,
        _vp, _vp, u64, _vp)
+    fn("val_frame_unpack_files_dev", i32, _vp, _vp, _vp, u64, u32, u32, u32, u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+       _vp, _vp, _vp, _vp, u64, _vp)
     fn("val_frame_accept", None, _vp, _vp, _vp, u32, u64, ctypes.POINTER(u64), _vp, ctypes.POINTER(u32),
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))

@@ -14,6 +14,11 @@
 //                   rolling file CRC state;
 //   k_unpack<G>     the hot path: every accepted payload copied to
 //                   file + dst[i]. k_pack with the hashing removed.
+// val_frame_unpack_files_dev delivers a window that holds frames of many
+// files through the same stages: one verify, one parse (which also marks
+// every frame as not accepted), k_unpack_order_files (a grid of workgroups,
+// each applying the rule to whole files, one after the other, and storing
+// absolute addresses in dst[i]) and one k_unpack<G> with file = NULL.
 // A payload may be written only when its own CRC matched (known after its last
 // byte was hashed) and its offset equals `written` (which depends on the
 // verdicts of every earlier frame), so the write cannot be fused into the
@@ -58,6 +63,13 @@ struct UnpackParams {
     uint32_t *naccepted;   // nullable, incremented
     uint32_t *noverflow;   // nullable, incremented
     const uint32_t *consts;
+    // val_frame_unpack_files_dev only: written, file_state, naccepted and
+    // noverflow are then arrays over the files, and file / file_cap are unused
+    uint32_t n_files;
+    const uint32_t *first;      // n_files + 1 frame indices
+    const uint64_t *file_ptr;   // the files' device addresses
+    const uint64_t *file_caps;
+    uint32_t *file_nbad;        // nullable, incremented
 };
 
 typedef uint32_t __attribute__((address_space(1))) uw32;
@@ -67,6 +79,9 @@ typedef uint8_t __attribute__((address_space(1))) uw8;
 // ---- header facts ----------------------------------------------------------
 // Exactly val_frame_data_offsets and val_frame_payload_lens for frame i, with
 // a frame that failed its CRC folded into NOT_DATA (it is never accepted).
+// FILES (val_frame_unpack_files_dev): a frame that no file owns is visited by
+// no order workgroup, so every frame starts as not accepted here.
+template <bool FILES>
 __global__ __launch_bounds__(256) void k_unpack_parse(const UnpackParams p)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -87,6 +102,10 @@ __global__ __launch_bounds__(256) void k_unpack_parse(const UnpackParams p)
     }
     p.foff[i] = fo;
     p.plen[i] = L >= pre ? L - pre : 0u;
+    if (FILES) {
+        p.dst[i] = VAL_FRAME_NOT_ACCEPTED;
+        if (p.accept) p.accept[i] = 0u;
+    }
 }
 
 // ---- ordering --------------------------------------------------------------
@@ -165,11 +184,11 @@ __device__ __forceinline__ uint32_t order_shift2(uint32_t v1, uint64_t n1, uint3
     return v1 ^ v2;
 }
 
-// The receiver's rule over frames 0..n-1 with state W = *written, in chunks of
-// one frame per thread. Within a chunk the frames are not walked one by one:
-// an exclusive scan of the candidates' payload lengths proposes every frame's
-// position; a find-first gives the next frame that can be accepted at the
-// known W (everything before it is skipped in that step), a second one the
+// The receiver's rule over frames first..last-1 with state W = *written, in
+// chunks of one frame per thread. Within a chunk the frames are not walked one
+// by one: an exclusive scan of the candidates' payload lengths proposes every
+// frame's position; a find-first gives the next frame that can be accepted at
+// the known W (everything before it is skipped in that step), a second one the
 // first later candidate that disagrees with its proposed position (everything
 // before it is accepted in that step). The cost is two barriers per accepted
 // run, whatever the number of skipped frames.
@@ -178,43 +197,74 @@ __device__ __forceinline__ uint32_t order_shift2(uint32_t v1, uint64_t n1, uint3
 // incoming state advances over the chunk's bytes (thread 0, beside its own frame),
 // and the XOR of all of them is the new state. A chunk accepts fewer than
 // 2^42 bytes, so every distance fits order_shift.
-__global__ __launch_bounds__(kOrderBlock) void k_unpack_order(const UnpackParams p)
+struct OrderShared {
+    uint64_t pos[kOrderBlock + 1];  // exclusive scan of candidate payload bytes; [kOrderBlock] = total
+    uint64_t wsum[kOrderBlock / 64];
+    uint64_t mask[2][2][kOrderBlock / 64];
+    uint32_t pow[kBlobPowMaps * 128];
+    uint32_t x, nacc;
+};
+static_assert(kBlobPowMaps * 128 % kOrderBlock == 0, "whole rounds of the workgroup copy the maps");
+
+// The blob's pow maps into LDS, once per workgroup. Published by the first
+// barrier of the first chunk (the scan's): the fold is the only reader.
+__device__ __forceinline__ void order_copy_pow(const UnpackParams &p, OrderShared &sh)
 {
-    __shared__ uint64_t s_pos[kOrderBlock + 1];  // exclusive scan of candidate payload bytes; [kOrderBlock] = total
-    __shared__ uint64_t s_wsum[kOrderBlock / 64];
-    __shared__ uint64_t s_mask[2][2][kOrderBlock / 64];
-    __shared__ uint32_t s_pow[kBlobPowMaps * 128];
-    __shared__ uint32_t s_x, s_nacc;
-    static_assert(kBlobPowMaps * 128 % kOrderBlock == 0, "whole rounds of the workgroup copy the maps");
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint64_t cap = p.file_cap;
-    uint64_t W = *p.written;
-    uint32_t state = p.file_state ? *p.file_state : 0u;  // thread 0's copy is the live one
-    uint32_t novf = 0, flip = 0;
-    if (t == 0) s_x = 0u, s_nacc = 0u;
-    if (p.file_state) {
 #pragma unroll
-        for (uint32_t r = 0; r < kBlobPowMaps * 128 / kOrderBlock; r++)
-            s_pow[r * kOrderBlock + t] = p.consts[kConstPow + r * kOrderBlock + t];
-    }
+    for (uint32_t r = 0; r < kBlobPowMaps * 128 / kOrderBlock; r++)
+        sh.pow[r * kOrderBlock + threadIdx.x] = p.consts[kConstPow + r * kOrderBlock + threadIdx.x];
+}
+
+// A value every lane holds alike, moved to scalar registers: what a workgroup
+// loads per file after its first stores comes per lane otherwise, and with
+// those in VGPRs k_unpack_order_files spilled.
+__device__ __forceinline__ uint64_t order_uniform(uint64_t v)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+}
+
+// One file's frames, by the whole workgroup. dst[i] = base + the frame's
+// offset in the file: base is 0 for k_unpack_order (the scatter adds p.file)
+// and the file's address for k_unpack_order_files. Everything a file's pass
+// keeps between chunks (W, the state, the counters, the ballot slot in turn,
+// the chunk loaded ahead, sh.x and sh.nacc) starts afresh here, and the
+// barrier in front of the results is also the one between this range's last
+// use of `sh` and the next range's first. FILES adds the per-file count of
+// failed trailers from ok[]; k_unpack_order does not load ok[] at all.
+template <bool FILES>
+__device__ __forceinline__ void order_range(const UnpackParams &p, OrderShared &sh, const uint64_t first,
+                                            const uint64_t last, const uint64_t cap, const uint64_t base,
+                                            uint64_t *written, uint32_t *file_state, uint32_t *naccepted,
+                                            uint32_t *noverflow, uint32_t *file_nbad)
+{
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    uint64_t W = *written;
+    uint32_t state = file_state ? *file_state : 0u;  // thread 0's copy is the live one
+    uint32_t novf = 0, flip = 0, nbad = 0;
+    if (t == 0) sh.x = 0u, sh.nacc = 0u;
     // the next chunk's header facts and payload state are loaded while this one is ordered
     uint64_t fo_n = VAL_FRAME_OFFSET_NOT_DATA;
     uint32_t pl_n = 0, py_n = 0;
-    if (t < p.n) {
-        fo_n = p.foff[t];
-        pl_n = p.plen[t];
-        if (p.file_state) py_n = p.pay[t];
+    uint32_t ok_n = 1;  // kept as loaded: a comparison here would wait for the load where it is issued
+    if (first + t < last) {
+        fo_n = p.foff[first + t];
+        pl_n = p.plen[first + t];
+        if (file_state) py_n = p.pay[first + t];
+        if (FILES) ok_n = p.ok[first + t];
     }
-    for (uint64_t c0 = 0; c0 < p.n; c0 += kOrderBlock) {
+    for (uint64_t c0 = first; c0 < last; c0 += kOrderBlock) {
         const uint64_t i = c0 + t;
-        const bool valid = i < p.n;
+        const bool valid = i < last;
         const uint64_t fo = fo_n;
         const uint32_t pl = pl_n, py = py_n;
-        fo_n = VAL_FRAME_OFFSET_NOT_DATA, pl_n = 0, py_n = 0;
-        if (i + kOrderBlock < p.n) {
+        if (FILES) nbad += (uint32_t)__builtin_popcountll(__ballot(ok_n == 0));
+        fo_n = VAL_FRAME_OFFSET_NOT_DATA, pl_n = 0, py_n = 0, ok_n = 1;
+        if (i + kOrderBlock < last) {
             fo_n = p.foff[i + kOrderBlock];
             pl_n = p.plen[i + kOrderBlock];
-            if (p.file_state) py_n = p.pay[i + kOrderBlock];
+            if (file_state) py_n = p.pay[i + kOrderBlock];
+            if (FILES) ok_n = p.ok[i + kOrderBlock];
         }
         const bool cand = fo != VAL_FRAME_OFFSET_NOT_DATA;
         const bool impl = fo == VAL_FRAME_OFFSET_IMPLIED;
@@ -226,18 +276,18 @@ __global__ __launch_bounds__(kOrderBlock) void k_unpack_order(const UnpackParams
             const uint64_t o = __shfl_up(incl, d);
             if ((int)lane >= d) incl += o;
         }
-        if (lane == 63u) s_wsum[wave] = incl;
+        if (lane == 63u) sh.wsum[wave] = incl;
         __syncthreads();
         uint64_t wbase = 0, total = 0;
 #pragma unroll
         for (uint32_t w = 0; w < kOrderBlock / 64; w++) {
-            const uint64_t v = s_wsum[w];
+            const uint64_t v = sh.wsum[w];
             if (w < wave) wbase += v;
             total += v;
         }
         const uint64_t pos = wbase + incl - mine;
-        s_pos[t] = pos;
-        if (t == 0) s_pos[kOrderBlock] = total;
+        sh.pos[t] = pos;
+        if (t == 0) sh.pos[kOrderBlock] = total;
         // (published by the barrier of the first order_first below)
         const uint64_t W0 = W;
         bool acc = false;
@@ -249,51 +299,80 @@ __global__ __launch_bounds__(kOrderBlock) void k_unpack_order(const UnpackParams
             const bool match = cand && t >= s && (impl || fo == W);
             const bool fits = W <= cap && (uint64_t)pl <= cap - W;
             uint32_t below = 0;
-            const uint32_t j = order_first(match && fits, match && !fits, s_mask[flip], &below);
+            const uint32_t j = order_first(match && fits, match && !fits, sh.mask[flip], &below);
             flip ^= 1u;
             novf += below;
             if (j == kOrderBlock) break;
             // every candidate from j on, placed as if all candidates before it were accepted
-            const uint64_t prop = W + (pos - s_pos[j]);
+            const uint64_t prop = W + (pos - sh.pos[j]);
             const bool agree = (impl || fo == prop) && prop <= cap && (uint64_t)pl <= cap - prop;
             uint32_t unused = 0;
-            const uint32_t b = order_first(cand && t > j && !agree, false, s_mask[flip], &unused);
+            const uint32_t b = order_first(cand && t > j && !agree, false, sh.mask[flip], &unused);
             flip ^= 1u;
             if (cand && t >= j && t < b) {
                 acc = true;
                 my_dst = prop;
             }
-            W += s_pos[b] - s_pos[j];  // b == kOrderBlock: the chunk's total
-            s = b;                     // frame b is judged against the new W in the next step
+            W += sh.pos[b] - sh.pos[j];  // b == kOrderBlock: the chunk's total
+            s = b;                       // frame b is judged against the new W in the next step
         }
         if (valid) {
-            p.dst[i] = acc ? my_dst : VAL_FRAME_NOT_ACCEPTED;
+            p.dst[i] = acc ? base + my_dst : VAL_FRAME_NOT_ACCEPTED;
             if (p.accept) p.accept[i] = acc ? 1u : 0u;
         }
         const uint64_t am = __ballot(acc);
-        if (lane == 0 && am) atomicAdd(&s_nacc, (uint32_t)__builtin_popcountll(am));
-        if (p.file_state && W != W0) {  // uniform: every thread tracks the same W
+        if (lane == 0 && am) atomicAdd(&sh.nacc, (uint32_t)__builtin_popcountll(am));
+        if (file_state && W != W0) {  // uniform: every thread tracks the same W
             uint32_t x = 0;
             const uint64_t after = W - (my_dst + pl);  // bytes accepted after this frame in the chunk
-            if (wave == 0) x = order_shift2(acc ? py : 0u, acc ? after : 0u, t == 0 ? state : 0u, t == 0 ? W - W0 : 0u, s_pow);
-            else if (acc && pl) x = order_shift(py, after, s_pow);
+            if (wave == 0) x = order_shift2(acc ? py : 0u, acc ? after : 0u, t == 0 ? state : 0u, t == 0 ? W - W0 : 0u, sh.pow);
+            else if (acc && pl) x = order_shift(py, after, sh.pow);
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) x ^= __shfl_xor(x, d);
-            if (lane == 0 && x) atomicXor(&s_x, x);
+            if (lane == 0 && x) atomicXor(&sh.x, x);
             __syncthreads();
             if (t == 0) {
-                state = s_x;
-                s_x = 0u;
+                state = sh.x;
+                sh.x = 0u;
             }
         }
         // the next chunk's first barrier (the scan's) orders these shared writes before its own
     }
     __syncthreads();
     if (t == 0) {
-        *p.written = W;
-        if (p.file_state) *p.file_state = state;
-        if (p.naccepted && s_nacc) atomicAdd(p.naccepted, s_nacc);
-        if (p.noverflow && novf) atomicAdd(p.noverflow, novf);
+        *written = W;
+        if (file_state) *file_state = state;
+        if (naccepted && sh.nacc) atomicAdd(naccepted, sh.nacc);
+        if (noverflow && novf) atomicAdd(noverflow, novf);
+    }
+    if (FILES && file_nbad && lane == 0 && nbad) atomicAdd(file_nbad, nbad);  // every wave saw its own 64 frames per chunk
+}
+
+// One file: the whole batch is its range.
+__global__ __launch_bounds__(kOrderBlock) void k_unpack_order(const UnpackParams p)
+{
+    __shared__ OrderShared sh;
+    if (p.file_state) order_copy_pow(p, sh);
+    order_range<false>(p, sh, 0, p.n, p.file_cap, 0, p.written, p.file_state, p.naccepted, p.noverflow, nullptr);
+}
+
+// Many files (val_frame_unpack_files_dev): workgroup b takes files b,
+// b + gridDim.x, ... one after the other; file s owns the frames
+// [first[s], first[s + 1]) clamped to [0, n] (a decreasing pair: none), and
+// written, file_state and the counters are arrays over the files. The maps
+// are copied once per workgroup. An empty file costs its two index reads.
+__global__ __launch_bounds__(kOrderBlock) void k_unpack_order_files(const UnpackParams p)
+{
+    __shared__ OrderShared sh;
+    if (p.file_state) order_copy_pow(p, sh);
+    for (uint64_t s = blockIdx.x; s < p.n_files; s += gridDim.x) {
+        const uint32_t a = p.first[s], b = p.first[s + 1];
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(a, p.n));
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(max(a, b), p.n));
+        if (lo >= hi) continue;
+        order_range<true>(p, sh, lo, hi, order_uniform(p.file_caps[s]), order_uniform(p.file_ptr[s]), p.written + s,
+                          p.file_state ? p.file_state + s : nullptr, p.naccepted ? p.naccepted + s : nullptr,
+                          p.noverflow ? p.noverflow + s : nullptr, p.file_nbad ? p.file_nbad + s : nullptr);
     }
 }
 

@@ -1677,6 +1677,83 @@ hipError_t launch_k_unpack(const UnpackParams &p, uint32_t cus, hipStream_t s)
 // offsets (u64), the payload states and lengths (u32), the verdicts (u8).
 uint64_t unpack_work_bytes(uint32_t n) { return ((uint64_t)n * 25u + 15u) & ~(uint64_t)15; }
 
+// The launches of both unpack calls on stream s: `u` holds the file side (one
+// file, or with `files` the per-file arrays); the frames, the workspace and
+// the per-frame outputs are filled in here. n > 0.
+val_status_t unpack_launch(Ctx &c, UnpackParams &u, bool files, const uint8_t *d_base, const uint64_t *d_off,
+                           const uint32_t *d_len, uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint,
+                           uint8_t *d_ok, uint32_t *d_nbad, uint8_t *d_accept, void *d_work, hipStream_t s)
+{
+    uint8_t *w = (uint8_t *)d_work;
+    u.base = d_base;
+    u.off = d_off;
+    u.len = d_len;
+    u.stride = stride;
+    u.flen = flen;
+    u.n = n;
+    u.dst = (uint64_t *)w;
+    u.foff = (uint64_t *)(w + (uint64_t)n * 8u);
+    uint32_t *pay = (uint32_t *)(w + (uint64_t)n * 16u);
+    u.pay = pay;
+    u.plen = (uint32_t *)(w + (uint64_t)n * 20u);
+    uint8_t *ok = d_ok ? d_ok : w + (uint64_t)n * 24u;
+    u.ok = ok;
+    u.accept = d_accept;
+    u.consts = c.d_consts;
+    // 1. verify: the launches of val_crc32_verify_frames_ex_dev
+    FrameParams p{};
+    p.base = d_base;
+    p.off = d_off;
+    p.len = d_len;
+    p.stride = stride;
+    p.flen = flen;
+    p.last_len = flen;
+    p.n = n;
+    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
+    p.xorout = 0xFFFFFFFFu;
+    p.verify = 1;
+    p.out_ok = ok;
+    p.nbad = d_nbad;
+    p.out_pay = pay;
+    const uint32_t typical_len = d_off ? len_hint : flen;
+    val_status_t st = launch_frames(c, p, typical_len, s);
+    if (st != VAL_OK) return st;
+    // 2. order: header facts grid-wide, then the receiver's rule: one workgroup for one file,
+    // else a workgroup per file up to one per CU
+    const dim3 pgrid((uint32_t)(((uint64_t)n + 255u) / 256u));
+    if (files) hipLaunchKernelGGL(k_unpack_parse<true>, pgrid, dim3(256), 0, s, u);
+    else hipLaunchKernelGGL(k_unpack_parse<false>, pgrid, dim3(256), 0, s, u);
+    VCRC_HIP(hipGetLastError(), "k_unpack_parse launch");
+    if (files) {
+        const uint32_t ogrid = std::min(u.n_files, (uint32_t)std::max(c.cus, 1));
+        hipLaunchKernelGGL(k_unpack_order_files, dim3(ogrid), dim3(kOrderBlock), 0, s, u);
+    } else {
+        hipLaunchKernelGGL(k_unpack_order, dim3(1), dim3(kOrderBlock), 0, s, u);
+    }
+    VCRC_HIP(hipGetLastError(), "k_unpack_order launch");
+    // 3. scatter
+    uint32_t lanes = forced_lanes();
+    if (!lanes) {
+        lanes = val_gpu_lanes_per_frame(typical_len ? typical_len : 1100u);
+        // as k_pack: a batch that leaves workgroups of the grid empty doubles its lanes until it fills them
+        const uint64_t threads = (uint64_t)std::max(c.cus, 1) * kUnpackBlocksPerCU * kUnpackBlock;
+        while (lanes < 64u && (uint64_t)n * lanes * 2u <= threads) lanes *= 2u;
+    }
+    hipError_t e = hipErrorInvalidValue;
+    switch (lanes) {
+    case 1: e = launch_k_unpack<1>(u, (uint32_t)c.cus, s); break;
+    case 2: e = launch_k_unpack<2>(u, (uint32_t)c.cus, s); break;
+    case 4: e = launch_k_unpack<4>(u, (uint32_t)c.cus, s); break;
+    case 8: e = launch_k_unpack<8>(u, (uint32_t)c.cus, s); break;
+    case 16: e = launch_k_unpack<16>(u, (uint32_t)c.cus, s); break;
+    case 32: e = launch_k_unpack<32>(u, (uint32_t)c.cus, s); break;
+    case 64: e = launch_k_unpack<64>(u, (uint32_t)c.cus, s); break;
+    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
+    }
+    VCRC_HIP(e, "k_unpack launch");
+    return VAL_OK;
+}
+
 }  // namespace vcrc
 
 using namespace vcrc;
@@ -2136,74 +2213,51 @@ val_status_t val_frame_unpack_batch_dev(const uint8_t *d_base, const uint64_t *d
     Ctx *c = nullptr;
     val_status_t st = cur_dev(stream, d_file, &c);
     if (st != VAL_OK) return st;
-    const hipStream_t s = pick_stream(stream);
-    uint8_t *w = (uint8_t *)d_work;
     UnpackParams u{};
-    u.base = d_base;
-    u.off = d_off;
-    u.len = d_len;
-    u.stride = stride;
-    u.flen = flen;
-    u.n = n;
     u.file = d_file;
     u.file_cap = file_cap;
-    u.dst = (uint64_t *)w;
-    u.foff = (uint64_t *)(w + (uint64_t)n * 8u);
-    uint32_t *pay = (uint32_t *)(w + (uint64_t)n * 16u);
-    u.pay = pay;
-    u.plen = (uint32_t *)(w + (uint64_t)n * 20u);
-    uint8_t *ok = d_ok ? d_ok : w + (uint64_t)n * 24u;
-    u.ok = ok;
     u.written = d_written;
     u.file_state = d_file_state;
-    u.accept = d_accept;
     u.naccepted = d_naccepted;
     u.noverflow = d_noverflow;
-    u.consts = c->d_consts;
-    // 1. verify: the launches of val_crc32_verify_frames_ex_dev
-    FrameParams p{};
-    p.base = d_base;
-    p.off = d_off;
-    p.len = d_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
-    p.verify = 1;
-    p.out_ok = ok;
-    p.nbad = d_nbad;
-    p.out_pay = pay;
-    const uint32_t typical_len = d_off ? len_hint : flen;
-    st = launch_frames(*c, p, typical_len, s);
+    return unpack_launch(*c, u, false, d_base, d_off, d_len, stride, flen, n, len_hint, d_ok, d_nbad, d_accept, d_work,
+                         pick_stream(stream));
+}
+
+val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                        uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint, uint32_t n_files,
+                                        const uint32_t *d_first, const uint64_t *d_file_ptr, const uint64_t *d_file_cap,
+                                        uint64_t *d_written, uint32_t *d_file_state, uint32_t *d_naccepted,
+                                        uint32_t *d_noverflow, uint32_t *d_file_nbad, uint8_t *d_ok, uint32_t *d_nbad,
+                                        uint8_t *d_accept, void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
+    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
+    if (work_bytes < unpack_work_bytes(n)) return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_unpack_work_bytes(n)");
+    if (n == 0 || n_files == 0) return VAL_OK;
+    if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
+    if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
+    if (!d_file_cap) return fail(VAL_ERR_INVALID_ARG, "file_cap is NULL");
+    if (!d_written) return fail(VAL_ERR_INVALID_ARG, "written is NULL");
+    if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    val_status_t st = cur_dev(stream, d_written, &c);
     if (st != VAL_OK) return st;
-    // 2. order: header facts grid-wide, then the receiver's rule in one workgroup
-    hipLaunchKernelGGL(k_unpack_parse, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, s, u);
-    VCRC_HIP(hipGetLastError(), "k_unpack_parse launch");
-    hipLaunchKernelGGL(k_unpack_order, dim3(1), dim3(kOrderBlock), 0, s, u);
-    VCRC_HIP(hipGetLastError(), "k_unpack_order launch");
-    // 3. scatter
-    uint32_t lanes = forced_lanes();
-    if (!lanes) {
-        lanes = val_gpu_lanes_per_frame(typical_len ? typical_len : 1100u);
-        // as k_pack: a batch that leaves workgroups of the grid empty doubles its lanes until it fills them
-        const uint64_t threads = (uint64_t)std::max(c->cus, 1) * kUnpackBlocksPerCU * kUnpackBlock;
-        while (lanes < 64u && (uint64_t)n * lanes * 2u <= threads) lanes *= 2u;
-    }
-    hipError_t e = hipErrorInvalidValue;
-    switch (lanes) {
-    case 1: e = launch_k_unpack<1>(u, (uint32_t)c->cus, s); break;
-    case 2: e = launch_k_unpack<2>(u, (uint32_t)c->cus, s); break;
-    case 4: e = launch_k_unpack<4>(u, (uint32_t)c->cus, s); break;
-    case 8: e = launch_k_unpack<8>(u, (uint32_t)c->cus, s); break;
-    case 16: e = launch_k_unpack<16>(u, (uint32_t)c->cus, s); break;
-    case 32: e = launch_k_unpack<32>(u, (uint32_t)c->cus, s); break;
-    case 64: e = launch_k_unpack<64>(u, (uint32_t)c->cus, s); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    VCRC_HIP(e, "k_unpack launch");
-    return VAL_OK;
+    UnpackParams u{};
+    u.n_files = n_files;
+    u.first = d_first;
+    u.file_ptr = d_file_ptr;
+    u.file_caps = d_file_cap;
+    u.written = d_written;
+    u.file_state = d_file_state;
+    u.naccepted = d_naccepted;
+    u.noverflow = d_noverflow;
+    u.file_nbad = d_file_nbad;
+    return unpack_launch(*c, u, true, d_base, d_off, d_len, stride, flen, n, len_hint, d_ok, d_nbad, d_accept, d_work,
+                         pick_stream(stream));
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

@@ -201,6 +201,67 @@ def unpack_data_batch_dev(base, *, file, written, off=None, length=None, stride:
     return out_ok, accept, counters[0], counters[1], counters[2]
 
 
+def unpack_data_files_dev(base, *, first, file_ptr, file_cap, written, off=None, length=None, stride: int = 0,
+                          flen: int = 0, n=None, len_hint: int = 0, file_state=None, naccepted=None, noverflow=None,
+                          file_nbad=None, out_ok=None, nbad=None, accept=None, work=None, stream=None):
+    """Verify a window that holds frames of many files and deliver every
+    file's accepted payloads (val_frame_unpack_files_dev): one verify, one
+    parse, one order launch over the files and one scatter on torch's current
+    stream (or ``stream``), returns at once. Per file the result is what
+    unpack_data_batch_dev leaves for that file's frames alone.
+
+    All tensors live on the GPU. ``base`` and the frames as in
+    unpack_data_batch_dev; the descriptors are grouped by file: file s owns
+    frames ``first[s]`` .. ``first[s + 1]`` (int32, S + 1 entries).
+    ``file_ptr`` int64[S] holds the files' device addresses (``t.data_ptr()``
+    of tensors the caller keeps alive), ``file_cap`` int64[S] their
+    capacities; ``written`` int64[S] and ``file_state`` int32[S] (raw
+    registers, optional) are read and updated in place, so calls chain.
+    ``naccepted``, ``noverflow`` and ``file_nbad`` (int32[S], incremented),
+    ``out_ok`` / ``accept`` uint8[n] and ``nbad`` (int32[1], incremented) are
+    allocated (counters zeroed) when not given; ``work`` is the workspace
+    (uint8, unpack_work_bytes(n)).
+    Returns (ok, accept, nbad, naccepted, noverflow, file_nbad).
+    """
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    if n is None:
+        n = int(off.numel()) if off is not None else 0
+    n_files = int(written.numel())
+    if int(first.numel()) != n_files + 1 or int(file_ptr.numel()) != n_files or int(file_cap.numel()) != n_files:
+        raise ValueError("first needs one entry more than written; file_ptr and file_cap as many")
+    dev = written.device
+    fresh = []
+    if out_ok is None:
+        out_ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        fresh.append(out_ok)
+    if accept is None:
+        accept = torch.empty(n, dtype=torch.uint8, device=dev)
+        fresh.append(accept)
+    if work is None:
+        work = torch.empty(max(unpack_work_bytes(n), 16), dtype=torch.uint8, device=dev)
+        fresh.append(work)
+    counters = []
+    for c, size in ((nbad, 1), (naccepted, n_files), (noverflow, n_files), (file_nbad, n_files)):
+        if c is None:
+            c = torch.zeros(size, dtype=torch.int32, device=dev)
+            fresh.append(c)
+        counters.append(c)
+    if stream is not None and fresh:  # allocations and zero fills are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_unpack_files_dev(_dptr(base), _dptr(off), _dptr(length), stride, flen, n, len_hint, n_files,
+                                          _dptr(first), _dptr(file_ptr), _dptr(file_cap), _dptr(written),
+                                          _dptr(file_state), _dptr(counters[1]), _dptr(counters[2]),
+                                          _dptr(counters[3]), _dptr(out_ok), _dptr(counters[0]), _dptr(accept),
+                                          _dptr(work), int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_frame_unpack_files_dev")
+    return out_ok, accept, counters[0], counters[1], counters[2], counters[3]
+
+
 def scan_frames(stream: np.ndarray, mtu: int, max_frames: int = 1 << 30):
     """Returns (status, frame_off, crc_len, consumed)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -243,5 +304,5 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
 
 
 __all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout",
-           "unpack_data_batch_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "payload_lens",
+           "unpack_data_batch_dev", "unpack_data_files_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "payload_lens",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

@@ -292,6 +292,63 @@ val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d
                                         uint32_t *d_noverflow, uint32_t *d_file_nbad, uint8_t *d_ok, uint32_t *d_nbad,
                                         uint8_t *d_accept, void *d_work, uint64_t work_bytes, void *stream);
 
+/* RX scan on the device, the step in front of the verify and unpack calls:
+ * received byte streams that lie in HBM are walked into frame descriptors
+ * without a host round trip. It replaces, for a whole window of every
+ * connection, the per-packet receive framing of the reference (the header
+ * read that tells the receiver how many bytes the frame has, and the
+ * content_len check of src/val_core.c:915-921), i.e. val_frame_scan (val_wire.h)
+ * once per stream. Async on `stream`; all pointers are device pointers;
+ * nothing is synchronised and no library scratch is kept.
+ * Stream s is d_base[d_stream_off[s], d_stream_off[s] + d_stream_len[s]), one
+ * per connection. For each stream the call leaves exactly what
+ * val_frame_scan(stream, len, mtu, max_frames, ...) returns for those bytes:
+ * d_nframes[s] the frame count, d_consumed[s] the bytes consumed (relative to
+ * the stream start: the bytes behind them are carried into the next window),
+ * d_status[s] VAL_OK or VAL_ERR_PROTOCOL (each array nullable), and the
+ * frames' (frame_off, crc_len) pairs with frame_off made absolute in d_base
+ * by adding d_stream_off[s]. The stop rules are the host's, in its order:
+ * max_frames reached; fewer than 8 bytes left; content_len > mtu - 12
+ * (VAL_ERR_PROTOCOL; the frames before it are kept); the frame is incomplete.
+ * Layout: the descriptors of all streams are compacted in stream order into
+ * d_frame_off / d_crc_len (n_streams * max_frames entries each);
+ * d_first[s] is the exclusive prefix sum of the counts and d_first[n_streams]
+ * the total (n_streams + 1 entries), so d_frame_off, d_crc_len and d_first
+ * feed val_frame_unpack_files_dev unchanged as d_off, d_len and d_first with
+ * n_files = n_streams. Entries [total, n_streams * max_frames) are set to
+ * (0, 0).
+ * Without reading the total back: pass n = n_streams * max_frames to
+ * val_frame_unpack_files_dev. By its clamping no file owns the padding
+ * entries; they are verified as zero-length frames at d_base and never
+ * delivered. Two conditions: such a caller passes d_nbad = NULL and reads the
+ * per-file d_file_nbad[], because the whole-batch counter would count the
+ * padding too (d_ok[i] of a padding entry says nothing); and d_base must hold
+ * at least 4 bytes, the trailer a zero-length frame at offset 0 is checked
+ * against.
+ * Only aligned dwords that overlap [stream start, stream start + len) are
+ * read, and of every header only the dwords that hold bytes 2..3. Positions
+ * are 64-bit. The walk advances 64 frames per memory round trip through runs
+ * of equal-size frames (up to 1,024 where a workgroup walks the stream,
+ * val_gpu_set_scan_front) and one frame per round trip where sizes alternate
+ * (DESIGN.md section 4.10).
+ * d_work: val_frame_scan_work_bytes(n_streams, max_frames) bytes, 8-byte
+ * aligned (every stream's descriptors before compaction, the counts); its
+ * contents after the call are unspecified. It must not overlap the outputs.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when mtu < 12, n_streams * max_frames overflows 32 bits, d_work is
+ * NULL or misaligned, work_bytes is below val_frame_scan_work_bytes, and, with
+ * n_streams > 0 and max_frames > 0, when d_stream_off, d_stream_len,
+ * d_frame_off, d_crc_len, d_first or d_base is NULL. Otherwise n_streams == 0
+ * returns VAL_OK and launches nothing; max_frames == 0 is valid: all counts,
+ * d_consumed and d_status are 0 and d_first (when given) is all zeros. The
+ * call runs on the stream's device (else the device d_base lives on). */
+uint64_t val_frame_scan_work_bytes(uint32_t n_streams, uint32_t max_frames);
+val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d_stream_off,
+                                        const uint64_t *d_stream_len, uint32_t n_streams, uint64_t mtu,
+                                        uint32_t max_frames, uint64_t *d_frame_off, uint32_t *d_crc_len,
+                                        uint32_t *d_first, uint32_t *d_nframes, uint64_t *d_consumed,
+                                        int32_t *d_status, void *d_work, uint64_t work_bytes, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8
@@ -491,6 +548,11 @@ val_status_t val_gpu_set_lanes_per_frame(uint32_t lanes);
  * for frames under 1,600 B,
  * 1 otherwise. Speed only; results never change. */
 val_status_t val_gpu_set_prefetch(int depth);
+/* Lanes that walk one stream in val_frame_scan_streams_dev: 64 (a wave per
+ * stream) or 1024 (a workgroup per stream); 0 = automatic: 1024 while the call
+ * has no more streams than the device has CUs, 64 beyond. Any other value
+ * returns VAL_ERR_INVALID_ARG. Speed only; results never change. */
+val_status_t val_gpu_set_scan_front(uint32_t lanes);
 /* Mixed-length descriptor batches (len_hint 0) of at least this many frames
  * are binned by length on the device; smaller ones run uniform. -1 restores
  * VAL_GPU_RAGGED_MIN_FRAMES from the environment (read once), else 4096.

@@ -31,6 +31,7 @@ VAL_OK = 0
 VAL_ERR_INVALID_ARG = -1
 VAL_ERR_NO_MEMORY = -2
 VAL_ERR_IO = -3
+VAL_ERR_PROTOCOL = -5
 VAL_ERR_CRC = -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +68,7 @@ EXPORTS = (
     "val_frame_data_batch_dev", "val_frame_data_layout",
     "val_frame_unpack_work_bytes", "val_frame_unpack_batch_dev", "val_frame_accept",
     "val_frame_unpack_files_dev",
+    "val_frame_scan_work_bytes", "val_frame_scan_streams_dev", "val_gpu_set_scan_front",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -187,6 +189,9 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
        _vp, _vp, u64, _vp)
     fn("val_frame_unpack_files_dev", i32, _vp, _vp, _vp, u64, u32, u32, u32, u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
        _vp, _vp, _vp, _vp, u64, _vp)
+    fn("val_gpu_set_scan_front", i32, u32)
+    fn("val_frame_scan_work_bytes", u64, u32, u32)
+    fn("val_frame_scan_streams_dev", i32, _vp, _vp, _vp, u32, u64, u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, u64, _vp)
     fn("val_frame_accept", None, _vp, _vp, _vp, u32, u64, ctypes.POINTER(u64), _vp, ctypes.POINTER(u32),
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
@@ -429,6 +434,12 @@ def set_geometry(lanes: int = 0, prefetch: int = -1) -> None:
 def set_lanes_per_frame(lanes: int) -> None:
     """Force the lanes-per-frame geometry (0 = automatic). Speed only."""
     _check(lib().val_gpu_set_lanes_per_frame(lanes), "val_gpu_set_lanes_per_frame")
+
+
+def set_scan_front(lanes: int) -> None:
+    """Force the lanes that walk one stream in wire.scan_streams_dev: 64 or
+    1024 (0 = automatic, by the number of streams). Speed only."""
+    _check(lib().val_gpu_set_scan_front(lanes), "val_gpu_set_scan_front")
 
 
 # ---- device-resident batches (torch tensors on the GPU) ---------------------

@@ -23,6 +23,7 @@
 #include "crc_kernels.hpp"
 #include "launch_plan.hpp"
 #include "pack_kernel.hpp"
+#include "scan_kernel.hpp"
 #include "unpack_kernel.hpp"
 #include "val_crc32_gpu.h"
 #include "val_protocol.h"
@@ -1754,6 +1755,19 @@ val_status_t unpack_launch(Ctx &c, UnpackParams &u, bool files, const uint8_t *d
     return VAL_OK;
 }
 
+// Workspace of val_frame_scan_streams_dev: every stream's slot of max_frames
+// descriptors (u64 offset, u32 length) and the streams' counts (u32). A
+// product beyond 32 bits, which the call refuses, asks for more than any
+// buffer holds.
+std::atomic<uint32_t> g_scan_front{0};  // val_gpu_set_scan_front: 0 = by the number of streams
+
+uint64_t scan_work_bytes(uint32_t n_streams, uint32_t max_frames)
+{
+    const uint64_t slots = (uint64_t)n_streams * max_frames;
+    if (slots > UINT32_MAX) return ~(uint64_t)7;
+    return (slots * 12u + (uint64_t)n_streams * 4u + 7u) & ~(uint64_t)7;
+}
+
 }  // namespace vcrc
 
 using namespace vcrc;
@@ -2258,6 +2272,94 @@ val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d
     u.file_nbad = d_file_nbad;
     return unpack_launch(*c, u, true, d_base, d_off, d_len, stride, flen, n, len_hint, d_ok, d_nbad, d_accept, d_work,
                          pick_stream(stream));
+}
+
+val_status_t val_gpu_set_scan_front(uint32_t lanes)
+{
+    if (lanes != 0 && lanes != 64u && lanes != 64u * kScanWideWaves)
+        return fail(VAL_ERR_INVALID_ARG, "scan front must be 0, 64 or 1024 lanes");
+    g_scan_front.store(lanes, std::memory_order_relaxed);
+    return VAL_OK;
+}
+
+uint64_t val_frame_scan_work_bytes(uint32_t n_streams, uint32_t max_frames)
+{
+    return scan_work_bytes(n_streams, max_frames);
+}
+
+val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d_stream_off,
+                                        const uint64_t *d_stream_len, uint32_t n_streams, uint64_t mtu,
+                                        uint32_t max_frames, uint64_t *d_frame_off, uint32_t *d_crc_len,
+                                        uint32_t *d_first, uint32_t *d_nframes, uint64_t *d_consumed,
+                                        int32_t *d_status, void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    if (mtu < VAL_WIRE_HEADER_SIZE + VAL_WIRE_TRAILER_SIZE) return fail(VAL_ERR_INVALID_ARG, "mtu below 12");
+    const uint64_t slots = (uint64_t)n_streams * max_frames;
+    if (slots > UINT32_MAX) return fail(VAL_ERR_INVALID_ARG, "n_streams * max_frames overflows 32 bits");
+    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
+    if (work_bytes < scan_work_bytes(n_streams, max_frames))
+        return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_scan_work_bytes(n_streams, max_frames)");
+    if (n_streams == 0) return VAL_OK;
+    if (max_frames > 0) {
+        if (!d_stream_off) return fail(VAL_ERR_INVALID_ARG, "stream_off is NULL");
+        if (!d_stream_len) return fail(VAL_ERR_INVALID_ARG, "stream_len is NULL");
+        if (!d_frame_off) return fail(VAL_ERR_INVALID_ARG, "frame_off is NULL");
+        if (!d_crc_len) return fail(VAL_ERR_INVALID_ARG, "crc_len is NULL");
+        if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
+        if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
+    }
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    val_status_t st = cur_dev(stream, d_base, &c);
+    if (st != VAL_OK) return st;
+    const hipStream_t s = pick_stream(stream);
+    if (max_frames == 0) {  // no stream is looked at: every count, consumed and status (VAL_OK) is 0
+        if (d_first) VCRC_HIP(hipMemsetAsync(d_first, 0, ((size_t)n_streams + 1u) * 4u, s), "memset(first)");
+        if (d_nframes) VCRC_HIP(hipMemsetAsync(d_nframes, 0, (size_t)n_streams * 4u, s), "memset(nframes)");
+        if (d_consumed) VCRC_HIP(hipMemsetAsync(d_consumed, 0, (size_t)n_streams * 8u, s), "memset(consumed)");
+        if (d_status) VCRC_HIP(hipMemsetAsync(d_status, 0, (size_t)n_streams * 4u, s), "memset(status)");
+        return VAL_OK;
+    }
+    uint8_t *w = (uint8_t *)d_work;
+    ScanParams p{};
+    p.base = d_base;
+    p.stream_off = d_stream_off;
+    p.stream_len = d_stream_len;
+    p.n_streams = n_streams;
+    p.max_frames = max_frames;
+    p.max_content = mtu - VAL_WIRE_HEADER_SIZE - VAL_WIRE_TRAILER_SIZE;
+    p.woff = (uint64_t *)w;
+    p.wlen = (uint32_t *)(w + slots * 8u);
+    p.wcnt = (uint32_t *)(w + slots * 12u);
+    p.frame_off = d_frame_off;
+    p.crc_len = d_crc_len;
+    p.first = d_first;
+    p.nframes = d_nframes;
+    p.consumed = d_consumed;
+    p.status = d_status;
+    // The walk, in a persistent grid: a workgroup of 16 waves per stream while every stream can
+    // have a CU of its own, else a wave per stream. Results do not depend on it.
+    const uint64_t cus = (uint64_t)std::max(c->cus, 1);
+    const uint64_t cap = cus * kScanBlocksPerCU;
+    uint32_t front = g_scan_front.load(std::memory_order_relaxed);
+    if (!front) front = n_streams <= cus ? 64u * kScanWideWaves : 64u;
+    if (front == 64u) {
+        constexpr uint32_t per = kScanBlock / 64;
+        const uint32_t wgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n_streams + per - 1) / per, cap);
+        hipLaunchKernelGGL(k_scan_streams<1>, dim3(wgrid), dim3(kScanBlock), 0, s, p);
+    } else {
+        const uint32_t wgrid = (uint32_t)std::min<uint64_t>(n_streams, cus * 2u);
+        hipLaunchKernelGGL(k_scan_streams<kScanWideWaves>, dim3(wgrid), dim3(64 * kScanWideWaves), 0, s, p);
+    }
+    VCRC_HIP(hipGetLastError(), "k_scan_streams launch");
+    hipLaunchKernelGGL(k_scan_first, dim3(1), dim3(kScanFirstBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_scan_first launch");
+    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((slots + kScanBlock - 1) / kScanBlock, cap);
+    hipLaunchKernelGGL(k_scan_compact, dim3(cgrid), dim3(kScanBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_scan_compact launch");
+    return VAL_OK;
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

@@ -275,6 +275,59 @@ def scan_frames(stream: np.ndarray, mtu: int, max_frames: int = 1 << 30):
     return st, frame_off[: nf.value], crc_len[: nf.value], used.value
 
 
+def scan_work_bytes(n_streams: int, max_frames: int) -> int:
+    """Workspace bytes scan_streams_dev needs."""
+    return int(lib().val_frame_scan_work_bytes(n_streams, max_frames))
+
+
+def scan_streams_dev(base, stream_off, stream_len, mtu: int, max_frames: int, *, stream=None):
+    """scan_frames for S byte streams that lie on the GPU
+    (val_frame_scan_streams_dev): three launches on torch's current stream (or
+    ``stream``), returns at once.
+
+    All tensors live on the GPU. Stream s is
+    ``base[stream_off[s] : stream_off[s] + stream_len[s]]`` (``base`` uint8,
+    ``stream_off`` / ``stream_len`` int64[S], uint64 bit patterns); at most
+    ``max_frames`` frames are taken from each. Returns (frame_off, crc_len,
+    first, nframes, consumed, status): ``frame_off`` int64 and ``crc_len``
+    int32 of S * max_frames entries, the streams' descriptors one after the
+    other with absolute offsets in ``base`` and (0, 0) behind the total;
+    ``first`` int32[S + 1], stream s owning entries ``first[s]`` ..
+    ``first[s + 1]``; ``nframes`` int32[S], ``consumed`` int64[S] (relative to
+    the stream start) and ``status`` int32[S] (VAL_OK or VAL_ERR_PROTOCOL) as
+    scan_frames reports them per stream. frame_off, crc_len and first feed
+    unpack_data_files_dev as ``off``, ``length`` and ``first``; with
+    ``n = S * max_frames`` nothing has to be read back in between (then read
+    ``file_nbad``, not ``nbad``, and keep ``base`` at 4 bytes or more).
+    """
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    S = int(stream_off.numel())
+    if int(stream_len.numel()) != S:
+        raise ValueError("stream_off and stream_len need one entry per stream")
+    slots = S * int(max_frames)
+    dev = base.device
+    frame_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    crc_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    first = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    nframes = torch.empty(S, dtype=torch.int32, device=dev)
+    consumed = torch.empty(S, dtype=torch.int64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    work = torch.empty(max(scan_work_bytes(S, max_frames), 16), dtype=torch.uint8, device=dev)
+    if stream is not None:  # the allocations are ordered before the launches
+        for t in (frame_off, crc_len, first, nframes, consumed, status, work):
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_scan_streams_dev(_dptr(base), _dptr(stream_off), _dptr(stream_len), S, mtu, max_frames,
+                                          _dptr(frame_off), _dptr(crc_len), _dptr(first), _dptr(nframes),
+                                          _dptr(consumed), _dptr(status), _dptr(work), int(work.numel()),
+                                          _stream_ptr(stream))
+    _check(st, "val_frame_scan_streams_dev")
+    return frame_off, crc_len, first, nframes, consumed, status
+
+
 def payload_lens(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     """Payload bytes of each frame (val_frame_payload_lens)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -304,5 +357,5 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
 
 
 __all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout",
-           "unpack_data_batch_dev", "unpack_data_files_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "payload_lens",
+           "unpack_data_batch_dev", "unpack_data_files_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "scan_streams_dev", "scan_work_bytes", "payload_lens",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

@@ -349,6 +349,75 @@ val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d
                                         uint32_t *d_first, uint32_t *d_nframes, uint64_t *d_consumed,
                                         int32_t *d_status, void *d_work, uint64_t work_bytes, void *stream);
 
+/* TX window fill on the device, the step in front of val_frame_data_batch_dev
+ * and the send-side counterpart of the scan call: the send state of n_files
+ * transfers whose files lie in HBM goes in, and the call leaves in HBM the wire
+ * bytes the reference sender's window-fill loop would have sent for each of
+ * them (src/val_sender.c:822-841 with send_data_packet, :258-315, and the
+ * explicit-offset rule of :833), trailers included, plus the descriptors the
+ * verify, scan and unpack calls consume. It replaces, for a whole window of
+ * every transfer, the host's per-transfer plan and the upload of
+ * val_frame_data_batch_dev's per-frame inputs. Async on `stream`; all pointers
+ * are device pointers; nothing is synchronised and no library scratch is kept.
+ * Addressing: file s is d_file_size[s] bytes at d_payload + d_file_pos[s],
+ * which is val_frame_data_batch_dev's addressing of a payload byte; the sum
+ * wraps modulo 2^64 by definition, so any device address can be expressed
+ * against any non-NULL d_payload.
+ * Per transfer s the call applies val_frame_fill_window (val_wire.h) with
+ * next = d_next[s], last_acked = d_last_acked[s], file_size = d_file_size[s],
+ * mtu, budget = min(d_budget[s], max_frames) (d_budget nullable = max_frames)
+ * and out_cap = d_stream_cap[s]. The frames it makes are written back to back
+ * from d_out + d_stream_off[s], byte for byte as val_frame_data_batch_dev
+ * writes them; d_next[s] becomes the rule's new next; d_nframes[s] the frame
+ * count and d_stream_len[s] the bytes used (each array nullable). With
+ * last_acked <= next only a call's first frame can be explicit
+ * (next == last_acked), so two calls on one stream chain: the second
+ * continues at the first's next with implied offsets. A go-back-N restart is
+ * d_next[s] = d_last_acked[s].
+ * Layout of the per-frame outputs, the scan call's: compacted in transfer
+ * order into arrays of n_files * max_frames entries; d_first[s] (n_files + 1
+ * entries) is the exclusive prefix sum of the counts and d_first[n_files] the
+ * total. d_frame_off[i] is the frame's start, absolute in d_out;
+ * d_crc_len[i] = 8 + content, d_crc[i] the trailer value, d_hdr[i] the
+ * header_crc (each nullable). Entries [total, n_files * max_frames) of all
+ * four are 0. d_out, d_frame_off, d_crc_len and d_first feed
+ * val_crc32_verify_frames_dev and val_frame_unpack_files_dev unchanged (with
+ * n = n_files * max_frames as described for the scan call); the wire bytes of
+ * transfer s, d_stream_off[s] and d_stream_len[s], feed
+ * val_frame_scan_streams_dev.
+ * Only the wire bytes of the frames made are written; every other byte of
+ * d_out keeps its value. Only aligned dwords that overlap a payload range are
+ * read from the files (val_frame_data_batch_dev's guarantees: the frames are
+ * built by the same kernel). Streams must not overlap each other or the files;
+ * that is the caller's promise.
+ * It is a short pipeline on the stream: a count
+ * launch of one thread per transfer (the rule is closed-form: every frame that
+ * does not end the file has wire size mtu), the prefix sum, a launch that
+ * writes val_frame_data_batch_dev's per-frame inputs into the workspace, and
+ * that call's launch over all n_files * max_frames entries, lanes picked from
+ * len_hint = mtu - 4 (val_gpu_set_lanes_per_frame forces them).
+ * d_work: val_frame_fill_work_bytes(n_files, max_frames) bytes, 8-byte
+ * aligned; its contents after the call are unspecified. It must not overlap
+ * the inputs or the outputs.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when mtu < 21 or mtu > 65547 (val_frame_fill_window's bounds),
+ * n_files * max_frames overflows 32 bits, d_work is NULL or misaligned,
+ * work_bytes is below val_frame_fill_work_bytes, and, with n_files > 0 and
+ * max_frames > 0, when d_payload, d_file_pos, d_file_size, d_next,
+ * d_last_acked, d_out, d_stream_off, d_stream_cap, d_first or d_frame_off is
+ * NULL. Otherwise n_files == 0 returns VAL_OK and launches nothing;
+ * max_frames == 0 is valid: d_nframes and d_stream_len are 0, d_first (when
+ * given) is all zeros and d_next is unchanged. The call runs on the stream's
+ * device (else the device d_out lives on). */
+uint64_t val_frame_fill_work_bytes(uint32_t n_files, uint32_t max_frames);
+val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *d_file_pos,
+                                      const uint64_t *d_file_size, uint64_t *d_next, const uint64_t *d_last_acked,
+                                      const uint32_t *d_budget, uint32_t n_files, uint64_t mtu, uint32_t max_frames,
+                                      uint8_t *d_out, const uint64_t *d_stream_off, const uint64_t *d_stream_cap,
+                                      uint64_t *d_stream_len, uint32_t *d_nframes, uint32_t *d_first,
+                                      uint64_t *d_frame_off, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
+                                      void *d_work, uint64_t work_bytes, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8

@@ -187,6 +187,43 @@ void val_frame_accept(const uint64_t *file_off, const uint32_t *pay_len, const u
                       uint64_t file_cap, uint64_t *written, uint64_t *dst_off, uint32_t *n_accepted,
                       uint32_t *n_overflow);
 
+/*
+ * The sender's window-fill rule (reference src/val_sender.c:822-841 with
+ * send_data_packet, :258-315, and the explicit-offset rule of :833), host
+ * only: which DATA frames a sender that stands at file offset `next`, whose
+ * last acknowledged offset is `last_acked`, puts into a window of at most
+ * `budget` frames and `out_cap` wire bytes of a file of `file_size` bytes.
+ * With M = mtu - 12, while fewer than `budget` frames were made and
+ * next < file_size: the frame is explicit (it carries its LE64 file offset)
+ * iff next == last_acked; last_acked does not move during the call, so with
+ * last_acked <= next, as a sender has it, only the call's first frame can be
+ * (a last_acked ahead of next makes the frame explicit that starts exactly
+ * there, if one does). Its payload is
+ * min(file_size - next, explicit ? M - 8 : M) bytes from file offset next, its
+ * content the payload plus 8 when explicit, its wire size 12 + content. A
+ * frame whose wire size exceeds what is left of out_cap ends the call without
+ * being made (judged as val_frame_accept does: need <= cap - used); otherwise
+ * it lies back to back behind the previous one and next advances by the
+ * payload. Every frame that does not end the file therefore has wire size mtu.
+ * Per frame i (arrays of `budget` entries, each nullable): file_off[i],
+ * pay_len[i], include_offset[i] (1 / 0), frame_off[i] (relative to the
+ * stream start) and crc_len[i] = 8 + content: the inputs and the placement of
+ * val_frame_data_batch / val_frame_data_batch_dev. *n_frames, *out_used (the
+ * stream's length) and *next_out (each nullable) are set. next >= file_size
+ * makes no frame and leaves *next_out = next. All arithmetic is 64-bit and
+ * never wraps. Returns VAL_ERR_INVALID_ARG, with the three results set to
+ * (0, 0, next), for mtu < 21 (the reference refuses an explicit frame whose
+ * payload room is 8 or less) and for mtu > 65547 (content would pass 65535,
+ * which the framer rejects). It states the rule val_frame_fill_files_dev
+ * (val_crc32_gpu.h) applies on the device.
+ */
+#define VAL_FILL_MTU_MIN 21u
+#define VAL_FILL_MTU_MAX (VAL_WIRE_MAX_CONTENT + VAL_WIRE_HEADER_SIZE + VAL_WIRE_TRAILER_SIZE)
+val_status_t val_frame_fill_window(uint64_t next, uint64_t last_acked, uint64_t file_size, uint64_t mtu,
+                                   uint32_t budget, uint64_t out_cap, uint64_t *file_off, uint32_t *pay_len,
+                                   uint8_t *include_offset, uint64_t *frame_off, uint32_t *crc_len,
+                                   uint32_t *n_frames, uint64_t *out_used, uint64_t *next_out);
+
 #ifdef __cplusplus
 }
 #endif

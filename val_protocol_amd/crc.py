@@ -69,6 +69,7 @@ EXPORTS = (
     "val_frame_unpack_work_bytes", "val_frame_unpack_batch_dev", "val_frame_accept",
     "val_frame_unpack_files_dev",
     "val_frame_scan_work_bytes", "val_frame_scan_streams_dev", "val_gpu_set_scan_front",
+    "val_frame_fill_window", "val_frame_fill_work_bytes", "val_frame_fill_files_dev",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -192,6 +193,11 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_gpu_set_scan_front", i32, u32)
     fn("val_frame_scan_work_bytes", u64, u32, u32)
     fn("val_frame_scan_streams_dev", i32, _vp, _vp, _vp, u32, u64, u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, u64, _vp)
+    fn("val_frame_fill_window", i32, u64, u64, u64, u64, u32, u64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(u32),
+       ctypes.POINTER(u64), ctypes.POINTER(u64))
+    fn("val_frame_fill_work_bytes", u64, u32, u32)
+    fn("val_frame_fill_files_dev", i32, _vp, _vp, _vp, _vp, _vp, _vp, u32, u64, u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+       _vp, _vp, _vp, _vp, u64, _vp)
     fn("val_frame_accept", None, _vp, _vp, _vp, u32, u64, ctypes.POINTER(u64), _vp, ctypes.POINTER(u32),
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))

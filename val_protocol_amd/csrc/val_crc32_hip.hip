@@ -21,6 +21,7 @@
 
 #include "cpu_crc32.h"
 #include "crc_kernels.hpp"
+#include "fill_kernel.hpp"
 #include "launch_plan.hpp"
 #include "pack_kernel.hpp"
 #include "scan_kernel.hpp"
@@ -1661,6 +1662,32 @@ hipError_t launch_k_pack(const PackParams &p, uint32_t cus, hipStream_t s)
     return hipGetLastError();
 }
 
+// The k_pack launch of a filled-in PackParams (p.n > 0) on stream s, shared by
+// val_frame_data_batch_dev and val_frame_fill_files_dev.
+val_status_t pack_launch(Ctx &c, const PackParams &p, uint32_t len_hint, hipStream_t s)
+{
+    uint32_t lanes = forced_lanes();
+    if (!lanes) {
+        lanes = val_gpu_lanes_per_frame(len_hint ? len_hint : 1100u);
+        // A batch that leaves workgroups of the grid empty doubles its lanes until it fills them
+        // (65,536 frames at 2 lanes are 128 of 256 workgroups).
+        while (lanes < 64u && (uint64_t)p.n * lanes * 2u <= (uint64_t)std::max(c.cus, 1) * kBlock) lanes *= 2u;
+    }
+    hipError_t e = hipErrorInvalidValue;
+    switch (lanes) {
+    case 1: e = launch_k_pack<1>(p, (uint32_t)c.cus, s); break;
+    case 2: e = launch_k_pack<2>(p, (uint32_t)c.cus, s); break;
+    case 4: e = launch_k_pack<4>(p, (uint32_t)c.cus, s); break;
+    case 8: e = launch_k_pack<8>(p, (uint32_t)c.cus, s); break;
+    case 16: e = launch_k_pack<16>(p, (uint32_t)c.cus, s); break;
+    case 32: e = launch_k_pack<32>(p, (uint32_t)c.cus, s); break;
+    case 64: e = launch_k_pack<64>(p, (uint32_t)c.cus, s); break;
+    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
+    }
+    VCRC_HIP(e, "k_pack launch");
+    return VAL_OK;
+}
+
 // Device unpacker (unpack_kernel.hpp): the scatter launch. Lanes per frame as
 // k_pack picks them; a persistent grid of at most kUnpackBlocksPerCU
 // workgroups per CU (the kernel holds no LDS and no scratch).
@@ -1766,6 +1793,17 @@ uint64_t scan_work_bytes(uint32_t n_streams, uint32_t max_frames)
     const uint64_t slots = (uint64_t)n_streams * max_frames;
     if (slots > UINT32_MAX) return ~(uint64_t)7;
     return (slots * 12u + (uint64_t)n_streams * 4u + 7u) & ~(uint64_t)7;
+}
+
+// Workspace of val_frame_fill_files_dev: k_pack's inputs for every slot (u64
+// payload and file offsets, u32 payload length, u8 explicit flag), and per
+// transfer its position before the call (u64) and its count (u32). A product
+// beyond 32 bits, which the call refuses, asks for more than any buffer holds.
+uint64_t fill_work_bytes(uint32_t n_files, uint32_t max_frames)
+{
+    const uint64_t slots = (uint64_t)n_files * max_frames;
+    if (slots > UINT32_MAX) return ~(uint64_t)7;
+    return (slots * 21u + (uint64_t)n_files * 12u + 7u) & ~(uint64_t)7;
 }
 
 }  // namespace vcrc
@@ -2184,27 +2222,7 @@ val_status_t val_frame_data_batch_dev(const uint8_t *d_payload, const uint64_t *
     p.out_hdr = d_hdr;
     p.nrejected = d_nrejected;
     p.consts = c->d_consts;
-    uint32_t lanes = forced_lanes();
-    if (!lanes) {
-        lanes = val_gpu_lanes_per_frame(len_hint ? len_hint : 1100u);
-        // A batch that leaves workgroups of the grid empty doubles its lanes until it fills them
-        // (65,536 frames at 2 lanes are 128 of 256 workgroups).
-        while (lanes < 64u && (uint64_t)n * lanes * 2u <= (uint64_t)std::max(c->cus, 1) * kBlock) lanes *= 2u;
-    }
-    const hipStream_t s = pick_stream(stream);
-    hipError_t e = hipErrorInvalidValue;
-    switch (lanes) {
-    case 1: e = launch_k_pack<1>(p, (uint32_t)c->cus, s); break;
-    case 2: e = launch_k_pack<2>(p, (uint32_t)c->cus, s); break;
-    case 4: e = launch_k_pack<4>(p, (uint32_t)c->cus, s); break;
-    case 8: e = launch_k_pack<8>(p, (uint32_t)c->cus, s); break;
-    case 16: e = launch_k_pack<16>(p, (uint32_t)c->cus, s); break;
-    case 32: e = launch_k_pack<32>(p, (uint32_t)c->cus, s); break;
-    case 64: e = launch_k_pack<64>(p, (uint32_t)c->cus, s); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    VCRC_HIP(e, "k_pack launch");
-    return VAL_OK;
+    return pack_launch(*c, p, len_hint, pick_stream(stream));
 }
 
 uint64_t val_frame_unpack_work_bytes(uint32_t n) { return unpack_work_bytes(n); }
@@ -2360,6 +2378,107 @@ val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d
     hipLaunchKernelGGL(k_scan_compact, dim3(cgrid), dim3(kScanBlock), 0, s, p);
     VCRC_HIP(hipGetLastError(), "k_scan_compact launch");
     return VAL_OK;
+}
+
+uint64_t val_frame_fill_work_bytes(uint32_t n_files, uint32_t max_frames)
+{
+    return fill_work_bytes(n_files, max_frames);
+}
+
+val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *d_file_pos,
+                                      const uint64_t *d_file_size, uint64_t *d_next, const uint64_t *d_last_acked,
+                                      const uint32_t *d_budget, uint32_t n_files, uint64_t mtu, uint32_t max_frames,
+                                      uint8_t *d_out, const uint64_t *d_stream_off, const uint64_t *d_stream_cap,
+                                      uint64_t *d_stream_len, uint32_t *d_nframes, uint32_t *d_first,
+                                      uint64_t *d_frame_off, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
+                                      void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    if (mtu < VAL_FILL_MTU_MIN) return fail(VAL_ERR_INVALID_ARG, "mtu below 21");
+    if (mtu > VAL_FILL_MTU_MAX) return fail(VAL_ERR_INVALID_ARG, "mtu above 65547");
+    const uint64_t slots = (uint64_t)n_files * max_frames;
+    if (slots > UINT32_MAX) return fail(VAL_ERR_INVALID_ARG, "n_files * max_frames overflows 32 bits");
+    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
+    if (work_bytes < fill_work_bytes(n_files, max_frames))
+        return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_fill_work_bytes(n_files, max_frames)");
+    if (n_files == 0) return VAL_OK;
+    if (max_frames > 0) {
+        if (!d_payload) return fail(VAL_ERR_INVALID_ARG, "payload is NULL");
+        if (!d_file_pos) return fail(VAL_ERR_INVALID_ARG, "file_pos is NULL");
+        if (!d_file_size) return fail(VAL_ERR_INVALID_ARG, "file_size is NULL");
+        if (!d_next) return fail(VAL_ERR_INVALID_ARG, "next is NULL");
+        if (!d_last_acked) return fail(VAL_ERR_INVALID_ARG, "last_acked is NULL");
+        if (!d_out) return fail(VAL_ERR_INVALID_ARG, "out is NULL");
+        if (!d_stream_off) return fail(VAL_ERR_INVALID_ARG, "stream_off is NULL");
+        if (!d_stream_cap) return fail(VAL_ERR_INVALID_ARG, "stream_cap is NULL");
+        if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
+        if (!d_frame_off) return fail(VAL_ERR_INVALID_ARG, "frame_off is NULL");
+    }
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    val_status_t st = cur_dev(stream, d_out, &c);
+    if (st != VAL_OK) return st;
+    const hipStream_t s = pick_stream(stream);
+    if (max_frames == 0) {  // no transfer is looked at: every count and length is 0, next stays
+        if (d_first) VCRC_HIP(hipMemsetAsync(d_first, 0, ((size_t)n_files + 1u) * 4u, s), "memset(first)");
+        if (d_nframes) VCRC_HIP(hipMemsetAsync(d_nframes, 0, (size_t)n_files * 4u, s), "memset(nframes)");
+        if (d_stream_len) VCRC_HIP(hipMemsetAsync(d_stream_len, 0, (size_t)n_files * 8u, s), "memset(stream_len)");
+        return VAL_OK;
+    }
+    uint8_t *w = (uint8_t *)d_work;
+    FillParams f{};
+    f.file_pos = d_file_pos;
+    f.file_size = d_file_size;
+    f.next = d_next;
+    f.last_acked = d_last_acked;
+    f.budget = d_budget;
+    f.n_files = n_files;
+    f.max_frames = max_frames;
+    f.mtu = mtu;
+    f.stream_off = d_stream_off;
+    f.stream_cap = d_stream_cap;
+    f.stream_len = d_stream_len;
+    f.nframes = d_nframes;
+    f.first = d_first;
+    f.frame_off = d_frame_off;
+    f.wpay_off = (uint64_t *)w;
+    f.wfile_off = (uint64_t *)(w + slots * 8u);
+    f.wnext = (uint64_t *)(w + slots * 16u);
+    f.wpay_len = (uint32_t *)(w + slots * 16u + (uint64_t)n_files * 8u);
+    f.wcnt = (uint32_t *)(w + slots * 20u + (uint64_t)n_files * 8u);
+    f.wexpl = w + slots * 20u + (uint64_t)n_files * 12u;
+    // 1. the counts, the streams' lengths and the new positions
+    const uint32_t ngrid = (uint32_t)(((uint64_t)n_files + kFillBlock - 1) / kFillBlock);
+    hipLaunchKernelGGL(k_fill_count, dim3(ngrid), dim3(kFillBlock), 0, s, f);
+    VCRC_HIP(hipGetLastError(), "k_fill_count launch");
+    // 2. d_first: the scan call's kernel over this call's counts
+    ScanParams sp{};
+    sp.n_streams = n_files;
+    sp.wcnt = f.wcnt;
+    sp.first = d_first;
+    hipLaunchKernelGGL(k_scan_first, dim3(1), dim3(kScanFirstBlock), 0, s, sp);
+    VCRC_HIP(hipGetLastError(), "k_scan_first launch");
+    // 3. k_pack's inputs, compacted in transfer order, the rest padded with rejects
+    const uint64_t cap = (uint64_t)std::max(c->cus, 1) * kFillBlocksPerCU;
+    const uint32_t dgrid = (uint32_t)std::min<uint64_t>((slots + kFillBlock - 1) / kFillBlock, cap);
+    hipLaunchKernelGGL(k_fill_desc, dim3(dgrid), dim3(kFillBlock), 0, s, f);
+    VCRC_HIP(hipGetLastError(), "k_fill_desc launch");
+    // 4. the frames: k_pack over every entry; a padding entry writes nothing and zeroes its outputs
+    PackParams p{};
+    p.payload = d_payload;
+    p.pay_off = f.wpay_off;
+    p.pay_len = f.wpay_len;
+    p.file_off = f.wfile_off;
+    p.include_offset = f.wexpl;
+    p.n = (uint32_t)slots;
+    p.out = d_out;
+    p.frame_off = d_frame_off;
+    p.out_len = d_crc_len;
+    p.out_crc = d_crc;
+    p.out_hdr = d_hdr;
+    p.consts = c->d_consts;
+    return pack_launch(*c, p, (uint32_t)(mtu - VAL_WIRE_TRAILER_SIZE), s);
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

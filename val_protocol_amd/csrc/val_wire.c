@@ -362,3 +362,48 @@ void val_frame_accept(const uint64_t *file_off, const uint32_t *pay_len, const u
     if (n_overflow)
         *n_overflow = overflow;
 }
+
+val_status_t val_frame_fill_window(uint64_t next, uint64_t last_acked, uint64_t file_size, uint64_t mtu,
+                                   uint32_t budget, uint64_t out_cap, uint64_t *file_off, uint32_t *pay_len,
+                                   uint8_t *include_offset, uint64_t *frame_off, uint32_t *crc_len,
+                                   uint32_t *n_frames, uint64_t *out_used, uint64_t *next_out)
+{
+    uint32_t k = 0;
+    uint64_t used = 0;
+    val_status_t st = VAL_OK;
+    if (mtu < VAL_FILL_MTU_MIN || mtu > VAL_FILL_MTU_MAX) {
+        st = VAL_ERR_INVALID_ARG;
+        budget = 0;
+    }
+    const uint64_t room = mtu - (VAL_WIRE_HEADER_SIZE + VAL_WIRE_TRAILER_SIZE); /* M; unused when refused */
+    while (k < budget && next < file_size) {
+        const int explicit_off = next == last_acked;
+        const uint64_t left = file_size - next;
+        const uint64_t most = explicit_off ? room - 8u : room;
+        const uint64_t pay = left < most ? left : most;
+        const uint64_t content = pay + (explicit_off ? 8u : 0u);
+        const uint64_t need = VAL_WIRE_HEADER_SIZE + content + VAL_WIRE_TRAILER_SIZE;
+        if (need > out_cap - used) /* used <= out_cap */
+            break;
+        if (file_off)
+            file_off[k] = next;
+        if (pay_len)
+            pay_len[k] = (uint32_t)pay;
+        if (include_offset)
+            include_offset[k] = (uint8_t)explicit_off;
+        if (frame_off)
+            frame_off[k] = used;
+        if (crc_len)
+            crc_len[k] = (uint32_t)(VAL_WIRE_HEADER_SIZE + content);
+        used += need;
+        next += pay; /* <= file_size */
+        k++;
+    }
+    if (n_frames)
+        *n_frames = k;
+    if (out_used)
+        *out_used = used;
+    if (next_out)
+        *next_out = next;
+    return st;
+}

@@ -328,6 +328,90 @@ def scan_streams_dev(base, stream_off, stream_len, mtu: int, max_frames: int, *,
     return frame_off, crc_len, first, nframes, consumed, status
 
 
+def fill_window(next: int, last_acked: int, file_size: int, mtu: int, budget: int, out_cap: int = (1 << 64) - 1):
+    """The sender's window-fill rule (val_frame_fill_window; host only): the
+    DATA frames a sender at file offset ``next`` puts into a window of at most
+    ``budget`` frames and ``out_cap`` wire bytes; the first one carries its
+    offset iff ``next == last_acked``. Returns (file_off uint64, pay_len
+    uint32, include_offset uint8, frame_off uint64 relative to the stream
+    start, crc_len uint32, used bytes, new next): the inputs of
+    build_data_batch / build_data_batch_dev and their placement. Raises
+    ValError for an mtu outside 21..65547."""
+    file_off = np.zeros(budget, dtype=np.uint64)
+    pay_len = np.zeros(budget, dtype=np.uint32)
+    inc = np.zeros(budget, dtype=np.uint8)
+    frame_off = np.zeros(budget, dtype=np.uint64)
+    crc_len = np.zeros(budget, dtype=np.uint32)
+    nf = ctypes.c_uint32(0)
+    used, nxt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = lib().val_frame_fill_window(next, last_acked, file_size, mtu, budget, out_cap, file_off.ctypes.data,
+                                     pay_len.ctypes.data, inc.ctypes.data, frame_off.ctypes.data, crc_len.ctypes.data,
+                                     ctypes.byref(nf), ctypes.byref(used), ctypes.byref(nxt))
+    _check(st, "val_frame_fill_window")
+    n = nf.value
+    return file_off[:n], pay_len[:n], inc[:n], frame_off[:n], crc_len[:n], int(used.value), int(nxt.value)
+
+
+def fill_work_bytes(n_files: int, max_frames: int) -> int:
+    """Workspace bytes fill_files_dev needs."""
+    return int(lib().val_frame_fill_work_bytes(n_files, max_frames))
+
+
+def fill_files_dev(payload, file_pos, file_size, next, last_acked, mtu: int, max_frames: int, *, out, stream_off,
+                   stream_cap, budget=None, out_hdr=None, work=None, stream=None):
+    """fill_window plus build_data_batch_dev for S transfers whose files lie on
+    the GPU (val_frame_fill_files_dev): four launches on torch's current
+    stream (or ``stream``), returns at once.
+
+    All tensors live on the GPU. File s is ``file_size[s]`` bytes at
+    ``payload.data_ptr() + file_pos[s]`` (``payload`` uint8; ``file_pos``,
+    ``file_size``, ``next``, ``last_acked`` int64[S], uint64 bit patterns;
+    ``budget`` int32[S], None: ``max_frames`` each). The frames of transfer s
+    go back to back to ``out[stream_off[s]:]``, at most ``stream_cap[s]``
+    bytes (int64[S]); ``next`` is updated in place, so calls chain. Returns
+    (frame_off, crc_len, crc, first, nframes, stream_len): ``frame_off`` int64
+    (absolute in ``out``), ``crc_len`` and ``crc`` int32 of S * max_frames
+    entries, the transfers' frames one after the other and zeros behind the
+    total; ``first`` int32[S + 1]; ``nframes`` int32[S] and ``stream_len``
+    int64[S]. ``out_hdr`` (int32, S * max_frames) receives header_crc.
+    ``out``, frame_off, crc_len and first feed unpack_data_files_dev and
+    crc.verify_frames; stream_off and stream_len feed scan_streams_dev.
+    """
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    S = int(next.numel())
+    for t in (file_pos, file_size, last_acked, stream_off, stream_cap):
+        if int(t.numel()) != S:
+            raise ValueError("file_pos, file_size, next, last_acked, stream_off and stream_cap need one entry per transfer")
+    if budget is not None and int(budget.numel()) != S:
+        raise ValueError("budget needs one entry per transfer")
+    slots = S * int(max_frames)
+    dev = out.device
+    frame_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    crc_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    crc = torch.empty(slots, dtype=torch.int32, device=dev)
+    first = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    nframes = torch.empty(S, dtype=torch.int32, device=dev)
+    stream_len = torch.empty(S, dtype=torch.int64, device=dev)
+    fresh = [frame_off, crc_len, crc, first, nframes, stream_len]
+    if work is None:
+        work = torch.empty(max(fill_work_bytes(S, max_frames), 16), dtype=torch.uint8, device=dev)
+        fresh.append(work)
+    if stream is not None:  # the allocations are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_fill_files_dev(_dptr(payload), _dptr(file_pos), _dptr(file_size), _dptr(next),
+                                        _dptr(last_acked), _dptr(budget), S, mtu, max_frames, _dptr(out),
+                                        _dptr(stream_off), _dptr(stream_cap), _dptr(stream_len), _dptr(nframes),
+                                        _dptr(first), _dptr(frame_off), _dptr(crc_len), _dptr(crc), _dptr(out_hdr),
+                                        _dptr(work), int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_frame_fill_files_dev")
+    return frame_off, crc_len, crc, first, nframes, stream_len
+
+
 def payload_lens(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     """Payload bytes of each frame (val_frame_payload_lens)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -358,4 +442,5 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
 
 __all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout",
            "unpack_data_batch_dev", "unpack_data_files_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "scan_streams_dev", "scan_work_bytes", "payload_lens",
+           "fill_window", "fill_files_dev", "fill_work_bytes",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

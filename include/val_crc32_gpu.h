@@ -589,7 +589,18 @@ enum {
     VAL_GPU_KERNEL_RAGGED = 0,    /* binned by length, then one grouped launch */
     VAL_GPU_KERNEL_SPLIT = 1,     /* one workgroup per frame */
     VAL_GPU_KERNEL_FRAMES = 2,    /* lanes per frame, persistent waves */
-    VAL_GPU_KERNEL_FRAMES_C0 = 3  /* the same with one-pass loads of round 0 */
+    VAL_GPU_KERNEL_FRAMES_C0 = 3, /* the same with one-pass loads of round 0 */
+    /* the window calls' kernels (val_gpu_plan_window) */
+    VAL_GPU_KERNEL_PACK = 4,
+    VAL_GPU_KERNEL_UNPACK_PARSE = 5,
+    VAL_GPU_KERNEL_UNPACK_ORDER = 6,
+    VAL_GPU_KERNEL_UNPACK_ORDER_FILES = 7,
+    VAL_GPU_KERNEL_UNPACK = 8,
+    VAL_GPU_KERNEL_SCAN_STREAMS = 9,
+    VAL_GPU_KERNEL_SCAN_FIRST = 10,
+    VAL_GPU_KERNEL_SCAN_COMPACT = 11,
+    VAL_GPU_KERNEL_FILL_COUNT = 12,
+    VAL_GPU_KERNEL_FILL_DESC = 13
 };
 typedef struct val_gpu_launch {
     uint32_t kernel;        /* VAL_GPU_KERNEL_* */
@@ -606,6 +617,19 @@ typedef struct val_gpu_launch {
 } val_gpu_launch_t;
 uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
                              uint32_t last_len, int want_payload, val_gpu_launch_t out_plan[2]);
+/* The launches one window call would make after its verify launches, if any
+ * (those are val_gpu_plan_frames), in order, with the process's current knobs
+ * (forced lanes, scan front); of a launch, kernel, lanes, grid and count (the
+ * entries the grid covers) are set, and for k_scan_streams lanes means lanes
+ * per stream. */
+enum { VAL_GPU_WINDOW_PACK = 0, VAL_GPU_WINDOW_UNPACK = 1, VAL_GPU_WINDOW_UNPACK_FILES = 2,
+       VAL_GPU_WINDOW_SCAN = 3, VAL_GPU_WINDOW_FILL = 4 };
+/* n: frames (pack, unpack) or streams / transfers (scan, fill); groups: files of
+ * UNPACK_FILES, else 0; max_frames: scan and fill, else 0; len_hint as the call takes
+ * it (strided unpack: flen; fill: the mtu). Needs no device. Returns the number of
+ * launches written: 0 for an unknown call or one that launches nothing. */
+uint32_t val_gpu_plan_window(uint32_t call, uint32_t cus, uint32_t n, uint32_t groups,
+                             uint32_t max_frames, uint32_t len_hint, val_gpu_launch_t out[4]);
 /* Force the lanes-per-frame geometry (1,2,4,...,64) for later calls of this
  * process; 0 restores the automatic choice. Returns VAL_ERR_INVALID_ARG for
  * other values. Results never depend on it; only speed does. */

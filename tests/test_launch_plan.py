@@ -468,6 +468,447 @@ def test_plan(knobs, cid, args, kn):
     assert [l[4] for l in got] == [0, got[0][5] if got else 0][:len(got)]
 
 
+# ---- the window calls (val_gpu_plan_window) ----------------------------------
+# The lanes and grids of the framer, both unpack calls, the scan and the fill,
+# pinned the same way: W_EXPECTED holds what the launch functions computed
+# before this arithmetic was moved out of them (their expressions, run as a
+# host program over this table); three rows (W_HAND) are also derived by hand
+# below. A row is a launch as (kernel, lanes, grid, count): kernel 4 k_pack,
+# 5 k_unpack_parse, 6 k_unpack_order, 7 k_unpack_order_files, 8 k_unpack,
+# 9 k_scan_streams (lanes per stream), 10 k_scan_first, 11 k_scan_compact,
+# 12 k_fill_count, 13 k_fill_desc.
+W_N = (1, 63, 64, 4096, 65535, 65536, 1 << 20)
+W_HINTS = (0, 600, 1100, 16400, 65532)
+W_STREAMS = (1, 256, 257, 100000)
+W_MAX_FRAMES = (1, 513)
+
+
+def _wcase(cid, call, cus, n, *, groups=0, max_frames=0, len_hint=0, **knobs):
+    return cid, dict(call=call, cus=cus, n=n, groups=groups, max_frames=max_frames, len_hint=len_hint), knobs
+
+
+def _window_cases():
+    c = []
+    for cus in (256, 8):
+        for name, call in (("pack", vc.WINDOW_PACK), ("unpack", vc.WINDOW_UNPACK)):
+            for n in W_N:
+                for hint in W_HINTS:
+                    c.append(_wcase(f"{name}-cus{cus}-n{n}-h{hint}", call, cus, n, len_hint=hint))
+                for lanes in (1, 64):
+                    c.append(_wcase(f"{name}-cus{cus}-n{n}-g{lanes}", call, cus, n, len_hint=1100, lanes=lanes))
+        for groups in (1, 255, 256, 257):
+            for n in (257, 65536):
+                c.append(_wcase(f"unpack-files-cus{cus}-n{n}-f{groups}", vc.WINDOW_UNPACK_FILES, cus, n, groups=groups,
+                                len_hint=1100))
+        for n in W_STREAMS:
+            for mf in W_MAX_FRAMES:
+                for front in (0, 64, 1024):
+                    c.append(_wcase(f"scan-cus{cus}-n{n}-m{mf}-front{front}", vc.WINDOW_SCAN, cus, n, max_frames=mf,
+                                    front=front))
+                for mtu in (21, 1024, 16396, 65547):
+                    c.append(_wcase(f"fill-cus{cus}-n{n}-m{mf}-mtu{mtu}", vc.WINDOW_FILL, cus, n, max_frames=mf,
+                                    len_hint=mtu))
+        # each side of k_fill_desc's persistent grid: cus * kFillBlocksPerCU workgroups of kFillBlock slots
+        full = cus * 8 * 256
+        for slots in (full - 256, full, full + 1):
+            c.append(_wcase(f"fill-cus{cus}-slots{slots}", vc.WINDOW_FILL, cus, 1, max_frames=slots, len_hint=1024))
+    # what launches nothing, and what is no call
+    c.append(_wcase("pack-n0", vc.WINDOW_PACK, 256, 0, len_hint=1100))
+    c.append(_wcase("unpack-files-f0", vc.WINDOW_UNPACK_FILES, 256, 64, groups=0, len_hint=1100))
+    c.append(_wcase("scan-m0", vc.WINDOW_SCAN, 256, 64, max_frames=0))
+    c.append(_wcase("fill-n0", vc.WINDOW_FILL, 256, 0, max_frames=8, len_hint=1024))
+    c.append(_wcase("fill-slots-overflow", vc.WINDOW_FILL, 256, 1 << 16, max_frames=1 << 16, len_hint=1024))
+    c.append(_wcase("unknown-call", 5, 256, 64, max_frames=8, len_hint=1024))
+    return c
+
+
+W_CASES = _window_cases()
+
+# Derived by hand from the launch functions this policy was moved out of:
+#  pack-cus256-n65536-h600: 600 B -> 2 lanes; 65,536 x 2 x 2 = 262,144 <= 256 x 1,024 threads: 4 lanes;
+#    65,536 x 4 x 2 is above: stays. 16 frames per wave: 4,096 groups in 256 workgroups of 16 waves, grid
+#    min(256, 256).
+#  scan-cus256-n257-m513-front0: 257 streams > 256 CUs: a wave per stream, 4 per workgroup: ceil(257 / 4) = 65
+#    workgroups <= 256 x 8. k_scan_first is one workgroup. 257 x 513 = 131,841 slots in
+#    ceil(131,841 / 256) = 516 workgroups <= 2,048.
+#  fill-cus8-n256-m513-mtu1024: 256 transfers in one workgroup of 256; k_scan_first one workgroup; 131,328
+#    slots are 513 workgroups, capped at 8 x 8 = 64. k_pack: content 1,020 B -> 2 lanes; 131,328 x 2 x 2 is
+#    above 8 x 1,024 threads: stays. 32 frames per wave: 4,104 groups in ceil(4,104 / 16) = 257 workgroups,
+#    capped at 8.
+W_HAND = {
+    "pack-cus256-n65536-h600": [(4, 4, 256, 65536)],
+    "scan-cus256-n257-m513-front0": [(9, 64, 65, 257), (10, 0, 1, 257), (11, 0, 516, 131841)],
+    "fill-cus8-n256-m513-mtu1024": [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 64, 131328), (4, 2, 8, 131328)],
+}
+
+W_EXPECTED = {
+    'pack-cus256-n1-h0': [(4, 64, 1, 1)],
+    'pack-cus256-n1-h600': [(4, 64, 1, 1)],
+    'pack-cus256-n1-h1100': [(4, 64, 1, 1)],
+    'pack-cus256-n1-h16400': [(4, 64, 1, 1)],
+    'pack-cus256-n1-h65532': [(4, 64, 1, 1)],
+    'pack-cus256-n1-g1': [(4, 1, 1, 1)],
+    'pack-cus256-n1-g64': [(4, 64, 1, 1)],
+    'pack-cus256-n63-h0': [(4, 64, 4, 63)],
+    'pack-cus256-n63-h600': [(4, 64, 4, 63)],
+    'pack-cus256-n63-h1100': [(4, 64, 4, 63)],
+    'pack-cus256-n63-h16400': [(4, 64, 4, 63)],
+    'pack-cus256-n63-h65532': [(4, 64, 4, 63)],
+    'pack-cus256-n63-g1': [(4, 1, 1, 63)],
+    'pack-cus256-n63-g64': [(4, 64, 4, 63)],
+    'pack-cus256-n64-h0': [(4, 64, 4, 64)],
+    'pack-cus256-n64-h600': [(4, 64, 4, 64)],
+    'pack-cus256-n64-h1100': [(4, 64, 4, 64)],
+    'pack-cus256-n64-h16400': [(4, 64, 4, 64)],
+    'pack-cus256-n64-h65532': [(4, 64, 4, 64)],
+    'pack-cus256-n64-g1': [(4, 1, 1, 64)],
+    'pack-cus256-n64-g64': [(4, 64, 4, 64)],
+    'pack-cus256-n4096-h0': [(4, 64, 256, 4096)],
+    'pack-cus256-n4096-h600': [(4, 64, 256, 4096)],
+    'pack-cus256-n4096-h1100': [(4, 64, 256, 4096)],
+    'pack-cus256-n4096-h16400': [(4, 64, 256, 4096)],
+    'pack-cus256-n4096-h65532': [(4, 64, 256, 4096)],
+    'pack-cus256-n4096-g1': [(4, 1, 4, 4096)],
+    'pack-cus256-n4096-g64': [(4, 64, 256, 4096)],
+    'pack-cus256-n65535-h0': [(4, 4, 256, 65535)],
+    'pack-cus256-n65535-h600': [(4, 4, 256, 65535)],
+    'pack-cus256-n65535-h1100': [(4, 4, 256, 65535)],
+    'pack-cus256-n65535-h16400': [(4, 8, 256, 65535)],
+    'pack-cus256-n65535-h65532': [(4, 16, 256, 65535)],
+    'pack-cus256-n65535-g1': [(4, 1, 64, 65535)],
+    'pack-cus256-n65535-g64': [(4, 64, 256, 65535)],
+    'pack-cus256-n65536-h0': [(4, 4, 256, 65536)],
+    'pack-cus256-n65536-h600': [(4, 4, 256, 65536)],
+    'pack-cus256-n65536-h1100': [(4, 4, 256, 65536)],
+    'pack-cus256-n65536-h16400': [(4, 8, 256, 65536)],
+    'pack-cus256-n65536-h65532': [(4, 16, 256, 65536)],
+    'pack-cus256-n65536-g1': [(4, 1, 64, 65536)],
+    'pack-cus256-n65536-g64': [(4, 64, 256, 65536)],
+    'pack-cus256-n1048576-h0': [(4, 4, 256, 1048576)],
+    'pack-cus256-n1048576-h600': [(4, 2, 256, 1048576)],
+    'pack-cus256-n1048576-h1100': [(4, 4, 256, 1048576)],
+    'pack-cus256-n1048576-h16400': [(4, 8, 256, 1048576)],
+    'pack-cus256-n1048576-h65532': [(4, 16, 256, 1048576)],
+    'pack-cus256-n1048576-g1': [(4, 1, 256, 1048576)],
+    'pack-cus256-n1048576-g64': [(4, 64, 256, 1048576)],
+    'unpack-cus256-n1-h0': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n1-h600': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n1-h1100': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n1-h16400': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n1-h65532': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n1-g1': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 1, 1, 1)],
+    'unpack-cus256-n1-g64': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus256-n63-h0': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n63-h600': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n63-h1100': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n63-h16400': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n63-h65532': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n63-g1': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 1, 1, 63)],
+    'unpack-cus256-n63-g64': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus256-n64-h0': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n64-h600': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n64-h1100': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n64-h16400': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n64-h65532': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n64-g1': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 1, 1, 64)],
+    'unpack-cus256-n64-g64': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus256-n4096-h0': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n4096-h600': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n4096-h1100': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n4096-h16400': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n4096-h65532': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n4096-g1': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 1, 16, 4096)],
+    'unpack-cus256-n4096-g64': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 1024, 4096)],
+    'unpack-cus256-n65535-h0': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 8, 2048, 65535)],
+    'unpack-cus256-n65535-h600': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 8, 2048, 65535)],
+    'unpack-cus256-n65535-h1100': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 8, 2048, 65535)],
+    'unpack-cus256-n65535-h16400': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 8, 2048, 65535)],
+    'unpack-cus256-n65535-h65532': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 16, 2048, 65535)],
+    'unpack-cus256-n65535-g1': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 1, 256, 65535)],
+    'unpack-cus256-n65535-g64': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 64, 2048, 65535)],
+    'unpack-cus256-n65536-h0': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 8, 2048, 65536)],
+    'unpack-cus256-n65536-h600': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 8, 2048, 65536)],
+    'unpack-cus256-n65536-h1100': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 8, 2048, 65536)],
+    'unpack-cus256-n65536-h16400': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 8, 2048, 65536)],
+    'unpack-cus256-n65536-h65532': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 16, 2048, 65536)],
+    'unpack-cus256-n65536-g1': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 1, 256, 65536)],
+    'unpack-cus256-n65536-g64': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 64, 2048, 65536)],
+    'unpack-cus256-n1048576-h0': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 4, 2048, 1048576)],
+    'unpack-cus256-n1048576-h600': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 2, 2048, 1048576)],
+    'unpack-cus256-n1048576-h1100': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 4, 2048, 1048576)],
+    'unpack-cus256-n1048576-h16400': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 8, 2048, 1048576)],
+    'unpack-cus256-n1048576-h65532': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 16, 2048, 1048576)],
+    'unpack-cus256-n1048576-g1': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 1, 2048, 1048576)],
+    'unpack-cus256-n1048576-g64': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 64, 2048, 1048576)],
+    'unpack-files-cus256-n257-f1': [(5, 0, 2, 257), (7, 0, 1, 1), (8, 64, 65, 257)],
+    'unpack-files-cus256-n65536-f1': [(5, 0, 256, 65536), (7, 0, 1, 1), (8, 8, 2048, 65536)],
+    'unpack-files-cus256-n257-f255': [(5, 0, 2, 257), (7, 0, 255, 255), (8, 64, 65, 257)],
+    'unpack-files-cus256-n65536-f255': [(5, 0, 256, 65536), (7, 0, 255, 255), (8, 8, 2048, 65536)],
+    'unpack-files-cus256-n257-f256': [(5, 0, 2, 257), (7, 0, 256, 256), (8, 64, 65, 257)],
+    'unpack-files-cus256-n65536-f256': [(5, 0, 256, 65536), (7, 0, 256, 256), (8, 8, 2048, 65536)],
+    'unpack-files-cus256-n257-f257': [(5, 0, 2, 257), (7, 0, 256, 257), (8, 64, 65, 257)],
+    'unpack-files-cus256-n65536-f257': [(5, 0, 256, 65536), (7, 0, 256, 257), (8, 8, 2048, 65536)],
+    'scan-cus256-n1-m1-front0': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'scan-cus256-n1-m1-front64': [(9, 64, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'scan-cus256-n1-m1-front1024': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'fill-cus256-n1-m1-mtu21': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus256-n1-m1-mtu1024': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus256-n1-m1-mtu16396': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus256-n1-m1-mtu65547': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'scan-cus256-n1-m513-front0': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'scan-cus256-n1-m513-front64': [(9, 64, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'scan-cus256-n1-m513-front1024': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'fill-cus256-n1-m513-mtu21': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 64, 33, 513)],
+    'fill-cus256-n1-m513-mtu1024': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 64, 33, 513)],
+    'fill-cus256-n1-m513-mtu16396': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 64, 33, 513)],
+    'fill-cus256-n1-m513-mtu65547': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 64, 33, 513)],
+    'scan-cus256-n256-m1-front0': [(9, 1024, 256, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'scan-cus256-n256-m1-front64': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'scan-cus256-n256-m1-front1024': [(9, 1024, 256, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'fill-cus256-n256-m1-mtu21': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 64, 16, 256)],
+    'fill-cus256-n256-m1-mtu1024': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 64, 16, 256)],
+    'fill-cus256-n256-m1-mtu16396': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 64, 16, 256)],
+    'fill-cus256-n256-m1-mtu65547': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 64, 16, 256)],
+    'scan-cus256-n256-m513-front0': [(9, 1024, 256, 256), (10, 0, 1, 256), (11, 0, 513, 131328)],
+    'scan-cus256-n256-m513-front64': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 513, 131328)],
+    'scan-cus256-n256-m513-front1024': [(9, 1024, 256, 256), (10, 0, 1, 256), (11, 0, 513, 131328)],
+    'fill-cus256-n256-m513-mtu21': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 513, 131328), (4, 2, 256, 131328)],
+    'fill-cus256-n256-m513-mtu1024': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 513, 131328), (4, 2, 256, 131328)],
+    'fill-cus256-n256-m513-mtu16396': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 513, 131328), (4, 8, 256, 131328)],
+    'fill-cus256-n256-m513-mtu65547': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 513, 131328), (4, 16, 256, 131328)],
+    'scan-cus256-n257-m1-front0': [(9, 64, 65, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'scan-cus256-n257-m1-front64': [(9, 64, 65, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'scan-cus256-n257-m1-front1024': [(9, 1024, 257, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'fill-cus256-n257-m1-mtu21': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 64, 17, 257)],
+    'fill-cus256-n257-m1-mtu1024': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 64, 17, 257)],
+    'fill-cus256-n257-m1-mtu16396': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 64, 17, 257)],
+    'fill-cus256-n257-m1-mtu65547': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 64, 17, 257)],
+    'scan-cus256-n257-m513-front0': [(9, 64, 65, 257), (10, 0, 1, 257), (11, 0, 516, 131841)],
+    'scan-cus256-n257-m513-front64': [(9, 64, 65, 257), (10, 0, 1, 257), (11, 0, 516, 131841)],
+    'scan-cus256-n257-m513-front1024': [(9, 1024, 257, 257), (10, 0, 1, 257), (11, 0, 516, 131841)],
+    'fill-cus256-n257-m513-mtu21': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 516, 131841), (4, 2, 256, 131841)],
+    'fill-cus256-n257-m513-mtu1024': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 516, 131841), (4, 2, 256, 131841)],
+    'fill-cus256-n257-m513-mtu16396': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 516, 131841), (4, 8, 256, 131841)],
+    'fill-cus256-n257-m513-mtu65547': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 516, 131841), (4, 16, 256, 131841)],
+    'scan-cus256-n100000-m1-front0': [(9, 64, 2048, 100000), (10, 0, 1, 100000), (11, 0, 391, 100000)],
+    'scan-cus256-n100000-m1-front64': [(9, 64, 2048, 100000), (10, 0, 1, 100000), (11, 0, 391, 100000)],
+    'scan-cus256-n100000-m1-front1024': [(9, 1024, 512, 100000), (10, 0, 1, 100000), (11, 0, 391, 100000)],
+    'fill-cus256-n100000-m1-mtu21': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 391, 100000), (4, 2, 196, 100000)],
+    'fill-cus256-n100000-m1-mtu1024': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 391, 100000), (4, 2, 196, 100000)],
+    'fill-cus256-n100000-m1-mtu16396': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 391, 100000), (4, 8, 256, 100000)],
+    'fill-cus256-n100000-m1-mtu65547': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 391, 100000), (4, 16, 256, 100000)],
+    'scan-cus256-n100000-m513-front0': [(9, 64, 2048, 100000), (10, 0, 1, 100000), (11, 0, 2048, 51300000)],
+    'scan-cus256-n100000-m513-front64': [(9, 64, 2048, 100000), (10, 0, 1, 100000), (11, 0, 2048, 51300000)],
+    'scan-cus256-n100000-m513-front1024': [(9, 1024, 512, 100000), (10, 0, 1, 100000), (11, 0, 2048, 51300000)],
+    'fill-cus256-n100000-m513-mtu21': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 2048, 51300000), (4, 2, 256, 51300000)],
+    'fill-cus256-n100000-m513-mtu1024': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 2048, 51300000), (4, 2, 256, 51300000)],
+    'fill-cus256-n100000-m513-mtu16396': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 2048, 51300000), (4, 8, 256, 51300000)],
+    'fill-cus256-n100000-m513-mtu65547': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 2048, 51300000), (4, 16, 256, 51300000)],
+    'fill-cus256-slots524032': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 2047, 524032), (4, 2, 256, 524032)],
+    'fill-cus256-slots524288': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 2048, 524288), (4, 2, 256, 524288)],
+    'fill-cus256-slots524289': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 2048, 524289), (4, 2, 256, 524289)],
+    'pack-cus8-n1-h0': [(4, 64, 1, 1)],
+    'pack-cus8-n1-h600': [(4, 64, 1, 1)],
+    'pack-cus8-n1-h1100': [(4, 64, 1, 1)],
+    'pack-cus8-n1-h16400': [(4, 64, 1, 1)],
+    'pack-cus8-n1-h65532': [(4, 64, 1, 1)],
+    'pack-cus8-n1-g1': [(4, 1, 1, 1)],
+    'pack-cus8-n1-g64': [(4, 64, 1, 1)],
+    'pack-cus8-n63-h0': [(4, 64, 4, 63)],
+    'pack-cus8-n63-h600': [(4, 64, 4, 63)],
+    'pack-cus8-n63-h1100': [(4, 64, 4, 63)],
+    'pack-cus8-n63-h16400': [(4, 64, 4, 63)],
+    'pack-cus8-n63-h65532': [(4, 64, 4, 63)],
+    'pack-cus8-n63-g1': [(4, 1, 1, 63)],
+    'pack-cus8-n63-g64': [(4, 64, 4, 63)],
+    'pack-cus8-n64-h0': [(4, 64, 4, 64)],
+    'pack-cus8-n64-h600': [(4, 64, 4, 64)],
+    'pack-cus8-n64-h1100': [(4, 64, 4, 64)],
+    'pack-cus8-n64-h16400': [(4, 64, 4, 64)],
+    'pack-cus8-n64-h65532': [(4, 64, 4, 64)],
+    'pack-cus8-n64-g1': [(4, 1, 1, 64)],
+    'pack-cus8-n64-g64': [(4, 64, 4, 64)],
+    'pack-cus8-n4096-h0': [(4, 4, 8, 4096)],
+    'pack-cus8-n4096-h600': [(4, 2, 8, 4096)],
+    'pack-cus8-n4096-h1100': [(4, 4, 8, 4096)],
+    'pack-cus8-n4096-h16400': [(4, 8, 8, 4096)],
+    'pack-cus8-n4096-h65532': [(4, 16, 8, 4096)],
+    'pack-cus8-n4096-g1': [(4, 1, 4, 4096)],
+    'pack-cus8-n4096-g64': [(4, 64, 8, 4096)],
+    'pack-cus8-n65535-h0': [(4, 4, 8, 65535)],
+    'pack-cus8-n65535-h600': [(4, 2, 8, 65535)],
+    'pack-cus8-n65535-h1100': [(4, 4, 8, 65535)],
+    'pack-cus8-n65535-h16400': [(4, 8, 8, 65535)],
+    'pack-cus8-n65535-h65532': [(4, 16, 8, 65535)],
+    'pack-cus8-n65535-g1': [(4, 1, 8, 65535)],
+    'pack-cus8-n65535-g64': [(4, 64, 8, 65535)],
+    'pack-cus8-n65536-h0': [(4, 4, 8, 65536)],
+    'pack-cus8-n65536-h600': [(4, 2, 8, 65536)],
+    'pack-cus8-n65536-h1100': [(4, 4, 8, 65536)],
+    'pack-cus8-n65536-h16400': [(4, 8, 8, 65536)],
+    'pack-cus8-n65536-h65532': [(4, 16, 8, 65536)],
+    'pack-cus8-n65536-g1': [(4, 1, 8, 65536)],
+    'pack-cus8-n65536-g64': [(4, 64, 8, 65536)],
+    'pack-cus8-n1048576-h0': [(4, 4, 8, 1048576)],
+    'pack-cus8-n1048576-h600': [(4, 2, 8, 1048576)],
+    'pack-cus8-n1048576-h1100': [(4, 4, 8, 1048576)],
+    'pack-cus8-n1048576-h16400': [(4, 8, 8, 1048576)],
+    'pack-cus8-n1048576-h65532': [(4, 16, 8, 1048576)],
+    'pack-cus8-n1048576-g1': [(4, 1, 8, 1048576)],
+    'pack-cus8-n1048576-g64': [(4, 64, 8, 1048576)],
+    'unpack-cus8-n1-h0': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n1-h600': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n1-h1100': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n1-h16400': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n1-h65532': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n1-g1': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 1, 1, 1)],
+    'unpack-cus8-n1-g64': [(5, 0, 1, 1), (6, 0, 1, 1), (8, 64, 1, 1)],
+    'unpack-cus8-n63-h0': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n63-h600': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n63-h1100': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n63-h16400': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n63-h65532': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n63-g1': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 1, 1, 63)],
+    'unpack-cus8-n63-g64': [(5, 0, 1, 63), (6, 0, 1, 63), (8, 64, 16, 63)],
+    'unpack-cus8-n64-h0': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n64-h600': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n64-h1100': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n64-h16400': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n64-h65532': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n64-g1': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 1, 1, 64)],
+    'unpack-cus8-n64-g64': [(5, 0, 1, 64), (6, 0, 1, 64), (8, 64, 16, 64)],
+    'unpack-cus8-n4096-h0': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 4, 64, 4096)],
+    'unpack-cus8-n4096-h600': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 4, 64, 4096)],
+    'unpack-cus8-n4096-h1100': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 4, 64, 4096)],
+    'unpack-cus8-n4096-h16400': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 8, 64, 4096)],
+    'unpack-cus8-n4096-h65532': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 16, 64, 4096)],
+    'unpack-cus8-n4096-g1': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 1, 16, 4096)],
+    'unpack-cus8-n4096-g64': [(5, 0, 16, 4096), (6, 0, 1, 4096), (8, 64, 64, 4096)],
+    'unpack-cus8-n65535-h0': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 4, 64, 65535)],
+    'unpack-cus8-n65535-h600': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 2, 64, 65535)],
+    'unpack-cus8-n65535-h1100': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 4, 64, 65535)],
+    'unpack-cus8-n65535-h16400': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 8, 64, 65535)],
+    'unpack-cus8-n65535-h65532': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 16, 64, 65535)],
+    'unpack-cus8-n65535-g1': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 1, 64, 65535)],
+    'unpack-cus8-n65535-g64': [(5, 0, 256, 65535), (6, 0, 1, 65535), (8, 64, 64, 65535)],
+    'unpack-cus8-n65536-h0': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 4, 64, 65536)],
+    'unpack-cus8-n65536-h600': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 2, 64, 65536)],
+    'unpack-cus8-n65536-h1100': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 4, 64, 65536)],
+    'unpack-cus8-n65536-h16400': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 8, 64, 65536)],
+    'unpack-cus8-n65536-h65532': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 16, 64, 65536)],
+    'unpack-cus8-n65536-g1': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 1, 64, 65536)],
+    'unpack-cus8-n65536-g64': [(5, 0, 256, 65536), (6, 0, 1, 65536), (8, 64, 64, 65536)],
+    'unpack-cus8-n1048576-h0': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 4, 64, 1048576)],
+    'unpack-cus8-n1048576-h600': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 2, 64, 1048576)],
+    'unpack-cus8-n1048576-h1100': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 4, 64, 1048576)],
+    'unpack-cus8-n1048576-h16400': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 8, 64, 1048576)],
+    'unpack-cus8-n1048576-h65532': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 16, 64, 1048576)],
+    'unpack-cus8-n1048576-g1': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 1, 64, 1048576)],
+    'unpack-cus8-n1048576-g64': [(5, 0, 4096, 1048576), (6, 0, 1, 1048576), (8, 64, 64, 1048576)],
+    'unpack-files-cus8-n257-f1': [(5, 0, 2, 257), (7, 0, 1, 1), (8, 32, 33, 257)],
+    'unpack-files-cus8-n65536-f1': [(5, 0, 256, 65536), (7, 0, 1, 1), (8, 4, 64, 65536)],
+    'unpack-files-cus8-n257-f255': [(5, 0, 2, 257), (7, 0, 8, 255), (8, 32, 33, 257)],
+    'unpack-files-cus8-n65536-f255': [(5, 0, 256, 65536), (7, 0, 8, 255), (8, 4, 64, 65536)],
+    'unpack-files-cus8-n257-f256': [(5, 0, 2, 257), (7, 0, 8, 256), (8, 32, 33, 257)],
+    'unpack-files-cus8-n65536-f256': [(5, 0, 256, 65536), (7, 0, 8, 256), (8, 4, 64, 65536)],
+    'unpack-files-cus8-n257-f257': [(5, 0, 2, 257), (7, 0, 8, 257), (8, 32, 33, 257)],
+    'unpack-files-cus8-n65536-f257': [(5, 0, 256, 65536), (7, 0, 8, 257), (8, 4, 64, 65536)],
+    'scan-cus8-n1-m1-front0': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'scan-cus8-n1-m1-front64': [(9, 64, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'scan-cus8-n1-m1-front1024': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 1, 1)],
+    'fill-cus8-n1-m1-mtu21': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus8-n1-m1-mtu1024': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus8-n1-m1-mtu16396': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'fill-cus8-n1-m1-mtu65547': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 1, 1), (4, 64, 1, 1)],
+    'scan-cus8-n1-m513-front0': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'scan-cus8-n1-m513-front64': [(9, 64, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'scan-cus8-n1-m513-front1024': [(9, 1024, 1, 1), (10, 0, 1, 1), (11, 0, 3, 513)],
+    'fill-cus8-n1-m513-mtu21': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 8, 5, 513)],
+    'fill-cus8-n1-m513-mtu1024': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 8, 5, 513)],
+    'fill-cus8-n1-m513-mtu16396': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 8, 5, 513)],
+    'fill-cus8-n1-m513-mtu65547': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 3, 513), (4, 16, 8, 513)],
+    'scan-cus8-n256-m1-front0': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'scan-cus8-n256-m1-front64': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'scan-cus8-n256-m1-front1024': [(9, 1024, 16, 256), (10, 0, 1, 256), (11, 0, 1, 256)],
+    'fill-cus8-n256-m1-mtu21': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 32, 8, 256)],
+    'fill-cus8-n256-m1-mtu1024': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 32, 8, 256)],
+    'fill-cus8-n256-m1-mtu16396': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 32, 8, 256)],
+    'fill-cus8-n256-m1-mtu65547': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 1, 256), (4, 32, 8, 256)],
+    'scan-cus8-n256-m513-front0': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 64, 131328)],
+    'scan-cus8-n256-m513-front64': [(9, 64, 64, 256), (10, 0, 1, 256), (11, 0, 64, 131328)],
+    'scan-cus8-n256-m513-front1024': [(9, 1024, 16, 256), (10, 0, 1, 256), (11, 0, 64, 131328)],
+    'fill-cus8-n256-m513-mtu21': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 64, 131328), (4, 2, 8, 131328)],
+    'fill-cus8-n256-m513-mtu1024': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 64, 131328), (4, 2, 8, 131328)],
+    'fill-cus8-n256-m513-mtu16396': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 64, 131328), (4, 8, 8, 131328)],
+    'fill-cus8-n256-m513-mtu65547': [(12, 0, 1, 256), (10, 0, 1, 256), (13, 0, 64, 131328), (4, 16, 8, 131328)],
+    'scan-cus8-n257-m1-front0': [(9, 64, 64, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'scan-cus8-n257-m1-front64': [(9, 64, 64, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'scan-cus8-n257-m1-front1024': [(9, 1024, 16, 257), (10, 0, 1, 257), (11, 0, 2, 257)],
+    'fill-cus8-n257-m1-mtu21': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 16, 5, 257)],
+    'fill-cus8-n257-m1-mtu1024': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 16, 5, 257)],
+    'fill-cus8-n257-m1-mtu16396': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 16, 5, 257)],
+    'fill-cus8-n257-m1-mtu65547': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 2, 257), (4, 16, 5, 257)],
+    'scan-cus8-n257-m513-front0': [(9, 64, 64, 257), (10, 0, 1, 257), (11, 0, 64, 131841)],
+    'scan-cus8-n257-m513-front64': [(9, 64, 64, 257), (10, 0, 1, 257), (11, 0, 64, 131841)],
+    'scan-cus8-n257-m513-front1024': [(9, 1024, 16, 257), (10, 0, 1, 257), (11, 0, 64, 131841)],
+    'fill-cus8-n257-m513-mtu21': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 64, 131841), (4, 2, 8, 131841)],
+    'fill-cus8-n257-m513-mtu1024': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 64, 131841), (4, 2, 8, 131841)],
+    'fill-cus8-n257-m513-mtu16396': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 64, 131841), (4, 8, 8, 131841)],
+    'fill-cus8-n257-m513-mtu65547': [(12, 0, 2, 257), (10, 0, 1, 257), (13, 0, 64, 131841), (4, 16, 8, 131841)],
+    'scan-cus8-n100000-m1-front0': [(9, 64, 64, 100000), (10, 0, 1, 100000), (11, 0, 64, 100000)],
+    'scan-cus8-n100000-m1-front64': [(9, 64, 64, 100000), (10, 0, 1, 100000), (11, 0, 64, 100000)],
+    'scan-cus8-n100000-m1-front1024': [(9, 1024, 16, 100000), (10, 0, 1, 100000), (11, 0, 64, 100000)],
+    'fill-cus8-n100000-m1-mtu21': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 100000), (4, 2, 8, 100000)],
+    'fill-cus8-n100000-m1-mtu1024': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 100000), (4, 2, 8, 100000)],
+    'fill-cus8-n100000-m1-mtu16396': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 100000), (4, 8, 8, 100000)],
+    'fill-cus8-n100000-m1-mtu65547': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 100000), (4, 16, 8, 100000)],
+    'scan-cus8-n100000-m513-front0': [(9, 64, 64, 100000), (10, 0, 1, 100000), (11, 0, 64, 51300000)],
+    'scan-cus8-n100000-m513-front64': [(9, 64, 64, 100000), (10, 0, 1, 100000), (11, 0, 64, 51300000)],
+    'scan-cus8-n100000-m513-front1024': [(9, 1024, 16, 100000), (10, 0, 1, 100000), (11, 0, 64, 51300000)],
+    'fill-cus8-n100000-m513-mtu21': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 51300000), (4, 2, 8, 51300000)],
+    'fill-cus8-n100000-m513-mtu1024': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 51300000), (4, 2, 8, 51300000)],
+    'fill-cus8-n100000-m513-mtu16396': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 51300000), (4, 8, 8, 51300000)],
+    'fill-cus8-n100000-m513-mtu65547': [(12, 0, 391, 100000), (10, 0, 1, 100000), (13, 0, 64, 51300000), (4, 16, 8, 51300000)],
+    'fill-cus8-slots16128': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 63, 16128), (4, 2, 8, 16128)],
+    'fill-cus8-slots16384': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 64, 16384), (4, 2, 8, 16384)],
+    'fill-cus8-slots16385': [(12, 0, 1, 1), (10, 0, 1, 1), (13, 0, 64, 16385), (4, 2, 8, 16385)],
+    'pack-n0': [],
+    'unpack-files-f0': [],
+    'scan-m0': [],
+    'fill-n0': [],
+    'fill-slots-overflow': [],
+    'unknown-call': [],
+}
+
+
+@pytest.fixture()
+def window_knobs():
+    """Sets the knobs the window plans honour for one case and restores them."""
+    def set_(lanes=0, front=0):
+        vc.set_lanes_per_frame(lanes)
+        vc.set_scan_front(front)
+
+    yield set_
+    set_()
+
+
+def test_window_table_is_complete():
+    ids = [cid for cid, _, _ in W_CASES]
+    assert len(set(ids)) == len(ids)
+    assert set(ids) == set(W_EXPECTED)
+    assert all(W_EXPECTED[k] == v for k, v in W_HAND.items())
+
+
+@pytest.mark.parametrize("cid,args,kn", W_CASES, ids=[c[0] for c in W_CASES])
+def test_window_plan(window_knobs, cid, args, kn):
+    window_knobs(**kn)
+    got = vc.plan_window(args["call"], args["cus"], args["n"], groups=args["groups"], max_frames=args["max_frames"],
+                         len_hint=args["len_hint"])
+    assert [(l.kernel, l.lanes, l.grid, l.count) for l in got] == W_EXPECTED[cid], (args, kn)
+    # a window launch sets nothing else
+    assert all((l.depth, l.first) + l.astuple()[6:] == (0,) * 8 for l in got)
+
+
 def test_defaults_are_what_the_table_assumes():
     """The table is pinned with the dynamic tail and the split kernel enabled
     (VAL_GPU_DYNAMIC_TAIL / VAL_GPU_SPLIT unset) and the default ragged minimum."""

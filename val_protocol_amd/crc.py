@@ -59,7 +59,7 @@ EXPORTS = (
     "val_gpu_scratch_entries", "val_gpu_set_host_batch_min_bytes", "val_gpu_host_batch_min_bytes",
     "val_gpu_host_batch_min_bytes_for",
     "val_gpu_cpu_batch_count", "val_gpu_set_host_cpu_threads", "val_gpu_host_multi_min_bytes", "val_gpu_host_multi_min_bytes_ex",
-    "val_gpu_set_tail_pieces", "val_gpu_tail_piece_launches", "val_gpu_plan_frames",
+    "val_gpu_set_tail_pieces", "val_gpu_tail_piece_launches", "val_gpu_plan_frames", "val_gpu_plan_window",
     "val_batch_attach", "val_batch_flush", "val_batch_get_stats", "val_batch_detach", "val_batch_crc32_provider",
     "val_serialize_handshake", "val_deserialize_handshake", "val_serialize_meta", "val_deserialize_meta",
     "val_serialize_resume_resp", "val_deserialize_resume_resp", "val_serialize_verify_request",
@@ -84,6 +84,10 @@ class ValError(RuntimeError):
 
 # val_gpu_launch_t.kernel
 KERNEL_RAGGED, KERNEL_SPLIT, KERNEL_FRAMES, KERNEL_FRAMES_C0 = 0, 1, 2, 3
+(KERNEL_PACK, KERNEL_UNPACK_PARSE, KERNEL_UNPACK_ORDER, KERNEL_UNPACK_ORDER_FILES, KERNEL_UNPACK, KERNEL_SCAN_STREAMS,
+ KERNEL_SCAN_FIRST, KERNEL_SCAN_COMPACT, KERNEL_FILL_COUNT, KERNEL_FILL_DESC) = range(4, 14)
+# val_gpu_plan_window: the window calls
+WINDOW_PACK, WINDOW_UNPACK, WINDOW_UNPACK_FILES, WINDOW_SCAN, WINDOW_FILL = range(5)
 
 
 class Launch(ctypes.Structure):
@@ -201,6 +205,7 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_frame_accept", None, _vp, _vp, _vp, u32, u64, ctypes.POINTER(u64), _vp, ctypes.POINTER(u32),
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
+    fn("val_gpu_plan_window", u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(Launch))
 
 
 def lib() -> ctypes.CDLL:
@@ -423,6 +428,16 @@ def plan_frames(cus: int, n: int, typical_len: int, *, descriptors: bool = False
     out = (Launch * 2)()
     k = lib().val_gpu_plan_frames(cus, n, int(descriptors), typical_len, flen, flen if last_len is None else last_len,
                                   int(want_payload), out)
+    return [out[i] for i in range(k)]
+
+
+def plan_window(call: int, cus: int, n: int, *, groups: int = 0, max_frames: int = 0, len_hint: int = 0) -> list:
+    """The launches (Launch, at most four: kernel, lanes, grid, count) of one
+    window call (WINDOW_*) after its verify launches, with the process's
+    current knobs. n: frames, or streams / transfers with max_frames; groups:
+    the files of WINDOW_UNPACK_FILES; len_hint: the fill's mtu. Needs no GPU."""
+    out = (Launch * 4)()
+    k = lib().val_gpu_plan_window(call, cus, n, groups, max_frames, len_hint, out)
     return [out[i] for i in range(k)]
 
 

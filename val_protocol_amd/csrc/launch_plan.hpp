@@ -1,10 +1,13 @@
-// launch_plan.hpp -- the frame-launch policy: which kernel a batch of frames
-// gets, with how many lanes, which round loop and which grid, and whether it
-// takes the dynamic tail, the in-launch tail pieces or the split kernel.
-// plan_frames() maps plain numbers to a LaunchPlan and calls no HIP API;
-// val_crc32_hip.hip launch_frames() executes a plan and decides nothing.
-// tests/test_launch_plan.py pins the plans of a table of shapes through
-// val_gpu_plan_frames(). Every threshold here is a measured result; the
+// launch_plan.hpp -- the launch policy: which kernel a batch of frames gets,
+// with how many lanes, which round loop and which grid, and whether it takes
+// the dynamic tail, the in-launch tail pieces or the split kernel
+// (plan_frames()); and the lanes and grids of the window calls' launches: the
+// framer, both unpack calls, the scan and the fill (plan_pack(),
+// plan_unpack(), plan_scan(), plan_fill()). They map plain numbers to
+// launches and call no HIP API; val_crc32_hip.hip fills in the kernels'
+// params, executes a plan and decides nothing. tests/test_launch_plan.py pins
+// the plans of a table of shapes through val_gpu_plan_frames() and
+// val_gpu_plan_window(). Every threshold here is a measured result; the
 // experiments are in DESIGN_EXPERIMENTS.md.
 #pragma once
 #include <stdint.h>
@@ -12,6 +15,10 @@
 #include <algorithm>
 
 #include "crc_kernels.hpp"
+#include "fill_kernel.hpp"
+#include "pack_kernel.hpp"
+#include "scan_kernel.hpp"
+#include "unpack_kernel.hpp"
 #include "val_crc32_gpu.h"
 
 namespace vcrc {
@@ -73,6 +80,7 @@ struct PlanKnobs {
     int forced_prefetch;    // -1 = none
     bool dyn_tail, split, tail_pieces;
     uint32_t ragged_min;
+    uint32_t scan_front;  // 0 = by the number of streams
 };
 
 using Launch = val_gpu_launch_t;
@@ -315,6 +323,114 @@ inline LaunchPlan plan_frames(uint32_t cus, uint32_t n, uint32_t typical_len, bo
                               uint32_t last_len, bool want_payload, const PlanKnobs &knobs)
 {
     return Planner{cus, descriptors, want_payload, flen, last_len, knobs}.frames(n, typical_len);
+}
+
+// ---- the window calls -------------------------------------------------------
+// Up to four launches on the caller's stream, in order. Their kernels use no
+// library scratch, so a launch is a kernel, its grid and, where the kernel is
+// instantiated by them, its lanes; count is the entries the grid covers.
+struct WindowPlan {
+    uint32_t count = 0;
+    Launch launch[4] = {};
+
+    void add(uint32_t kernel, uint64_t grid, uint64_t entries, uint32_t lanes = 0)
+    {
+        Launch &l = launch[count++];
+        l.kernel = kernel;
+        l.lanes = lanes;
+        l.grid = (uint32_t)grid;
+        l.count = (uint32_t)entries;
+    }
+};
+
+// Lanes per frame of k_pack and k_unpack: forced (val_gpu_set_lanes_per_frame),
+// else from len_hint as the hash kernels choose them; without a hint, the
+// geometry of MTU-sized frames, which is correct for every length. `threads`
+// is the kernel's whole persistent grid.
+inline uint32_t window_lanes(uint32_t n, uint32_t len_hint, uint64_t threads, const PlanKnobs &k)
+{
+    uint32_t lanes = k.forced_lanes;
+    if (!lanes) {
+        lanes = Planner{0, false, false, 0, 0, k}.lanes_per_frame(len_hint ? len_hint : 1100u);
+        // A batch that leaves workgroups of the grid empty doubles its lanes until it fills them
+        // (65,536 frames at 2 lanes are 128 of 256 workgroups).
+        while (lanes < 64u && (uint64_t)n * lanes * 2u <= threads) lanes *= 2u;
+    }
+    return lanes;
+}
+
+// Device framer (pack_kernel.hpp): one k_pack launch over n entries, after
+// the launches of `pl` (the fill's). A persistent grid of at most one
+// workgroup per CU; the kernel uses no scratch.
+inline WindowPlan plan_pack(uint32_t cus, uint32_t n, uint32_t len_hint, const PlanKnobs &k, WindowPlan pl = {})
+{
+    if (n == 0) return pl;
+    const uint32_t G = window_lanes(n, len_hint, (uint64_t)std::max(cus, 1u) * kBlock, k);
+    const uint64_t groups = ((uint64_t)n + (64 / G) - 1) / (64 / G);
+    const uint64_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
+    pl.add(VAL_GPU_KERNEL_PACK, std::min<uint64_t>(blocks, std::max(cus, 1u)), n, G);
+    return pl;
+}
+
+// Device unpacker (unpack_kernel.hpp), after the verify launches (plan_frames
+// with typical_len): the header facts grid-wide, then the receiver's rule: one
+// workgroup for one file, else (files) a workgroup per file up to one per CU;
+// then the scatter, lanes per frame as k_pack picks them, in a persistent grid
+// of at most kUnpackBlocksPerCU workgroups per CU (the kernel holds no LDS and
+// no scratch).
+inline WindowPlan plan_unpack(uint32_t cus, uint32_t n, bool files, uint32_t n_files, uint32_t typical_len,
+                              const PlanKnobs &k)
+{
+    WindowPlan pl;
+    if (n == 0 || (files && n_files == 0)) return pl;
+    pl.add(VAL_GPU_KERNEL_UNPACK_PARSE, ((uint64_t)n + 255u) / 256u, n);
+    if (files) pl.add(VAL_GPU_KERNEL_UNPACK_ORDER_FILES, std::min(n_files, std::max(cus, 1u)), n_files);
+    else pl.add(VAL_GPU_KERNEL_UNPACK_ORDER, 1, n);
+    // as k_pack: a batch that leaves workgroups of the grid empty doubles its lanes until it fills them
+    const uint64_t threads = (uint64_t)std::max(cus, 1u) * kUnpackBlocksPerCU * kUnpackBlock;
+    const uint32_t G = window_lanes(n, typical_len, threads, k);
+    const uint64_t groups = ((uint64_t)n + (64 / G) - 1) / (64 / G);
+    const uint64_t blocks = (groups + (kUnpackBlock / 64) - 1) / (kUnpackBlock / 64);
+    pl.add(VAL_GPU_KERNEL_UNPACK, std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1u) * kUnpackBlocksPerCU), n, G);
+    return pl;
+}
+
+// Device frame scan (scan_kernel.hpp). The walk, in a persistent grid: a
+// workgroup of 16 waves per stream while every stream can have a CU of its
+// own, else a wave per stream (the launch's lanes are
+// the lanes per stream). Results do not depend on it. A slot product beyond
+// 32 bits, which the call refuses, has no plan.
+inline WindowPlan plan_scan(uint32_t cus32, uint32_t n_streams, uint32_t max_frames, const PlanKnobs &k)
+{
+    WindowPlan pl;
+    const uint64_t slots = (uint64_t)n_streams * max_frames;
+    if (slots == 0 || slots > UINT32_MAX) return pl;
+    const uint64_t cus = (uint64_t)std::max(cus32, 1u);
+    const uint64_t cap = cus * kScanBlocksPerCU;
+    uint32_t front = k.scan_front;
+    if (!front) front = n_streams <= cus ? 64u * kScanWideWaves : 64u;
+    constexpr uint32_t per = kScanBlock / 64;
+    const uint64_t wgrid = front == 64u ? std::min<uint64_t>(((uint64_t)n_streams + per - 1) / per, cap)
+                                        : std::min<uint64_t>(n_streams, cus * 2u);
+    pl.add(VAL_GPU_KERNEL_SCAN_STREAMS, wgrid, n_streams, front);
+    pl.add(VAL_GPU_KERNEL_SCAN_FIRST, 1, n_streams);
+    pl.add(VAL_GPU_KERNEL_SCAN_COMPACT, std::min<uint64_t>((slots + kScanBlock - 1) / kScanBlock, cap), slots);
+    return pl;
+}
+
+// Device window fill (fill_kernel.hpp): the counts, d_first by the scan call's
+// kernel, k_pack's inputs for every slot in a persistent grid, then k_pack
+// over every slot with the content of a full frame as its hint.
+inline WindowPlan plan_fill(uint32_t cus, uint32_t n_files, uint32_t max_frames, uint64_t mtu, const PlanKnobs &k)
+{
+    WindowPlan pl;
+    const uint64_t slots = (uint64_t)n_files * max_frames;
+    if (slots == 0 || slots > UINT32_MAX) return pl;
+    pl.add(VAL_GPU_KERNEL_FILL_COUNT, ((uint64_t)n_files + kFillBlock - 1) / kFillBlock, n_files);
+    pl.add(VAL_GPU_KERNEL_SCAN_FIRST, 1, n_files);
+    const uint64_t cap = (uint64_t)std::max(cus, 1u) * kFillBlocksPerCU;
+    pl.add(VAL_GPU_KERNEL_FILL_DESC, std::min<uint64_t>((slots + kFillBlock - 1) / kFillBlock, cap), slots);
+    return plan_pack(cus, (uint32_t)slots, (uint32_t)(mtu - VAL_WIRE_TRAILER_SIZE), k, pl);
 }
 
 }  // namespace vcrc

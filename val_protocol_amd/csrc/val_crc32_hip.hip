@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "cpu_crc32.h"
@@ -142,6 +143,58 @@ val_status_t fail(val_status_t st, const char *what, hipError_t e = hipSuccess)
         if (e_ != hipSuccess) return fail(VAL_ERR_IO, what, e_); \
     } while (0)
 
+// ---- argument checks the entry points share ---------------------------------
+// Descriptors come as a pair.
+val_status_t check_off_len(const uint64_t *off, const uint32_t *len)
+{
+    if ((off == nullptr) != (len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
+    return VAL_OK;
+}
+
+// The slots of a window call, n * max_frames, index 32-bit arrays; `what`
+// names the product.
+val_status_t check_slots(uint32_t n, uint32_t max_frames, const char *what)
+{
+    if ((uint64_t)n * max_frames > UINT32_MAX) return fail(VAL_ERR_INVALID_ARG, what);
+    return VAL_OK;
+}
+
+// A caller-owned workspace of at least `need` bytes; `below` is the text for
+// one that is smaller.
+val_status_t check_work(const void *d_work, uint64_t work_bytes, uint64_t need, const char *below)
+{
+    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
+    if (work_bytes < need) return fail(VAL_ERR_INVALID_ARG, below);
+    return VAL_OK;
+}
+
+// A window call with max_frames == 0 looks at nothing: every count is 0, and
+// so is the call's u64 per stream or transfer (`what64` names its memset).
+val_status_t zero_window_outputs(uint32_t n, uint32_t *d_first, uint32_t *d_nframes, uint64_t *d_u64,
+                                 const char *what64, hipStream_t s)
+{
+    if (d_first) VCRC_HIP(hipMemsetAsync(d_first, 0, ((size_t)n + 1u) * 4u, s), "memset(first)");
+    if (d_nframes) VCRC_HIP(hipMemsetAsync(d_nframes, 0, (size_t)n * 4u, s), "memset(nframes)");
+    if (d_u64) VCRC_HIP(hipMemsetAsync(d_u64, 0, (size_t)n * 8u, s), what64);
+    return VAL_OK;
+}
+
+// The regions of a caller-owned workspace, taken in order: a layout written
+// as its takes gives the pointers (base = d_work) and the bytes (base = null)
+// from one statement.
+struct Carve {
+    uintptr_t base;
+    uint64_t used = 0;
+    template <typename T>
+    T *take(uint64_t count)
+    {
+        T *p = reinterpret_cast<T *>(base + used);
+        used += count * sizeof(T);
+        return p;
+    }
+};
+
 void ctx_free(Ctx &c);
 
 val_status_t ctx_init(Ctx &c, int device)
@@ -258,8 +311,29 @@ val_status_t cur_dev(void *stream, const void *ptr, Ctx **out)
 
 bool valid_lanes(uint32_t g) { return g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64; }
 
+// A run-time lane count as the kernels' template argument: launch(G), G a
+// std::integral_constant, returns the launch's HIP status (`what` names it).
+template <typename F>
+val_status_t launch_at_lanes(uint32_t lanes, const char *what, F &&launch)
+{
+    hipError_t e = hipSuccess;
+    switch (lanes) {
+    case 1: e = launch(std::integral_constant<int, 1>{}); break;
+    case 2: e = launch(std::integral_constant<int, 2>{}); break;
+    case 4: e = launch(std::integral_constant<int, 4>{}); break;
+    case 8: e = launch(std::integral_constant<int, 8>{}); break;
+    case 16: e = launch(std::integral_constant<int, 16>{}); break;
+    case 32: e = launch(std::integral_constant<int, 32>{}); break;
+    case 64: e = launch(std::integral_constant<int, 64>{}); break;
+    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
+    }
+    VCRC_HIP(e, what);
+    return VAL_OK;
+}
+
 std::atomic<uint32_t> g_forced_lanes{0};
 std::atomic<int> g_forced_prefetch{-1};
+std::atomic<uint32_t> g_scan_front{0};  // val_gpu_set_scan_front: 0 = by the number of streams
 
 uint32_t env_u32(const char *name)
 {
@@ -386,20 +460,11 @@ val_status_t launch_uniform_one(Ctx &c, FrameParams &p, const Launch &l, hipStre
         p.qparts = l.qparts;
         p.static_rounds = l.static_rounds;
     }
-    hipError_t e = hipSuccess;
-    switch (l.lanes) {
-    case 1: e = launch_k_frames<1>(l, used, s, p); break;
-    case 2: e = launch_k_frames<2>(l, used, s, p); break;
-    case 4: e = launch_k_frames<4>(l, used, s, p); break;
-    case 8: e = launch_k_frames<8>(l, used, s, p); break;
-    case 16: e = launch_k_frames<16>(l, used, s, p); break;
-    case 32: e = launch_k_frames<32>(l, used, s, p); break;
-    case 64: e = launch_k_frames<64>(l, used, s, p); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    if (p.tail_n && e == hipSuccess) used->tail.counts_zero = true;
-    VCRC_HIP(e, "k_frames launch");
-    return VAL_OK;
+    return launch_at_lanes(l.lanes, "k_frames launch", [&](auto G) {
+        const hipError_t e = launch_k_frames<decltype(G)::value>(l, used, s, p);
+        if (p.tail_n && e == hipSuccess) used->tail.counts_zero = true;
+        return e;
+    });
 }
 
 void arena_free(Arena &a);
@@ -596,7 +661,7 @@ uint32_t ragged_min_frames()
 PlanKnobs plan_knobs()
 {
     return PlanKnobs{forced_lanes(), forced_prefetch(), dyn_tail_enabled(), split_enabled(), tail_pieces_enabled(),
-                     ragged_min_frames()};
+                     ragged_min_frames(), g_scan_front.load(std::memory_order_relaxed)};
 }
 
 // Frames [l.first, l.first + l.count) of batch p as a batch of their own, with
@@ -646,6 +711,24 @@ val_status_t launch_frames(Ctx &c, FrameParams &p, uint32_t typical_len, hipStre
         if (l.tail_n) g_tail_piece_launches.fetch_add(1, std::memory_order_relaxed);
     }
     return VAL_OK;
+}
+
+// A batch of DATA frames (descriptors, or strided with every frame flen long)
+// under the protocol's CRC-32; the outputs and verify are the caller's.
+FrameParams data_frames(const uint8_t *base, const uint64_t *off, const uint32_t *len, uint64_t stride, uint32_t flen,
+                        uint32_t n)
+{
+    FrameParams p{};
+    p.base = base;
+    p.off = off;
+    p.len = len;
+    p.stride = stride;
+    p.flen = flen;
+    p.last_len = flen;
+    p.n = n;
+    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
+    p.xorout = 0xFFFFFFFFu;
+    return p;
 }
 
 // NULL selects the HIP default (null) stream, as in every HIP API.
@@ -1046,16 +1129,7 @@ val_status_t frames_host_small(Ctx &c, const uint8_t *base, uint64_t lo, uint64_
     uint32_t *h_hdr = h_crc + n;
     uint32_t *h_pay = h_hdr + n;
     uint8_t *h_ok = reinterpret_cast<uint8_t *>(h_pay + n + 4);
-    FrameParams p{};
-    p.base = frames;
-    p.off = h_off;
-    p.len = h_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
+    FrameParams p = data_frames(frames, h_off, h_len, stride, flen, n);
     p.out_crc = crc ? h_crc : nullptr;
     p.out_hdr = hdr ? h_hdr : nullptr;
     p.verify = verify ? 1u : 0u;
@@ -1196,7 +1270,7 @@ val_status_t frames_host(const uint8_t *base, uint64_t base_len, const uint64_t 
                          uint8_t *ok, uint32_t *nbad, uint32_t *pay = nullptr, bool route_cpu = true)
 {
     if (!base && n) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
-    if ((off == nullptr) != (len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
+    if (val_status_t st = check_off_len(off, len); st != VAL_OK) return st;
     const uint64_t tail = verify ? 4u : 0u;
     uint32_t lmin = UINT32_MAX, lmax = 0;
     uint64_t total = 0;
@@ -1310,17 +1384,9 @@ val_status_t frames_host(const uint8_t *base, uint64_t base_len, const uint64_t 
         }
         VCRC_HIP(hipEventRecord(c.h2d_done[k], cs), "hipEventRecord");
         VCRC_HIP(hipStreamWaitEvent(s, c.h2d_done[k], 0), "hipStreamWaitEvent");
-        FrameParams p{};
-        p.base = c.d_slot[k] - ch.lo;  // the kernel only touches base + off within the slot
-        p.off = d_off ? d_off + ch.i0 : nullptr;
-        p.len = d_len ? d_len + ch.i0 : nullptr;
-        if (!off) p.base = c.d_slot[k];  // strided: frame i0 is at the slot start
-        p.stride = stride;
-        p.flen = flen;
-        p.last_len = flen;
-        p.n = ch.i1 - ch.i0;
-        p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-        p.xorout = 0xFFFFFFFFu;
+        // descriptors: the kernel only touches base + off within the slot; strided: frame i0 is at the slot start
+        FrameParams p = data_frames(off ? c.d_slot[k] - ch.lo : c.d_slot[k], d_off ? d_off + ch.i0 : nullptr,
+                                    d_len ? d_len + ch.i0 : nullptr, stride, flen, ch.i1 - ch.i0);
         p.out_crc = crc ? d_crc + ch.i0 : nullptr;
         p.out_hdr = hdr ? d_hdr + ch.i0 : nullptr;
         p.verify = verify ? 1u : 0u;
@@ -1449,7 +1515,7 @@ val_status_t frames_host_multi(const uint8_t *base, uint64_t base_len, const uin
                                uint8_t *ok, uint32_t *nbad, int ndev)
 {
     if (!base && n) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
-    if ((off == nullptr) != (len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
+    if (val_status_t st = check_off_len(off, len); st != VAL_OK) return st;
     const uint64_t tail = verify ? 4u : 0u;
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -1646,64 +1712,47 @@ void ctx_free(Ctx &c)
     if (c.stream) (void)hipStreamDestroy(c.stream);
 }
 
-// Device framer (pack_kernel.hpp): one k_pack launch on the caller's stream.
-// Lanes per frame: forced (val_gpu_set_lanes_per_frame), else from len_hint as
-// the hash kernels choose them; without a hint, the geometry of MTU-sized
-// frames, which is correct for every length; a batch too small to fill the
-// grid doubles them until it does. A persistent grid of at most one workgroup
-// per CU; the kernel uses no scratch.
-template <int G>
-hipError_t launch_k_pack(const PackParams &p, uint32_t cus, hipStream_t s)
+// The planned k_pack launch (launch_plan.hpp plan_pack) of a filled-in
+// PackParams on stream s, shared by val_frame_data_batch_dev and
+// val_frame_fill_files_dev.
+val_status_t pack_launch(const PackParams &p, const Launch &l, hipStream_t s)
 {
-    const uint64_t groups = ((uint64_t)p.n + (64 / G) - 1) / (64 / G);
-    const uint64_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, std::max(cus, 1u));
-    hipLaunchKernelGGL(k_pack<G>, dim3(grid), dim3(kBlock), 0, s, p);
-    return hipGetLastError();
-}
-
-// The k_pack launch of a filled-in PackParams (p.n > 0) on stream s, shared by
-// val_frame_data_batch_dev and val_frame_fill_files_dev.
-val_status_t pack_launch(Ctx &c, const PackParams &p, uint32_t len_hint, hipStream_t s)
-{
-    uint32_t lanes = forced_lanes();
-    if (!lanes) {
-        lanes = val_gpu_lanes_per_frame(len_hint ? len_hint : 1100u);
-        // A batch that leaves workgroups of the grid empty doubles its lanes until it fills them
-        // (65,536 frames at 2 lanes are 128 of 256 workgroups).
-        while (lanes < 64u && (uint64_t)p.n * lanes * 2u <= (uint64_t)std::max(c.cus, 1) * kBlock) lanes *= 2u;
-    }
-    hipError_t e = hipErrorInvalidValue;
-    switch (lanes) {
-    case 1: e = launch_k_pack<1>(p, (uint32_t)c.cus, s); break;
-    case 2: e = launch_k_pack<2>(p, (uint32_t)c.cus, s); break;
-    case 4: e = launch_k_pack<4>(p, (uint32_t)c.cus, s); break;
-    case 8: e = launch_k_pack<8>(p, (uint32_t)c.cus, s); break;
-    case 16: e = launch_k_pack<16>(p, (uint32_t)c.cus, s); break;
-    case 32: e = launch_k_pack<32>(p, (uint32_t)c.cus, s); break;
-    case 64: e = launch_k_pack<64>(p, (uint32_t)c.cus, s); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    VCRC_HIP(e, "k_pack launch");
-    return VAL_OK;
-}
-
-// Device unpacker (unpack_kernel.hpp): the scatter launch. Lanes per frame as
-// k_pack picks them; a persistent grid of at most kUnpackBlocksPerCU
-// workgroups per CU (the kernel holds no LDS and no scratch).
-template <int G>
-hipError_t launch_k_unpack(const UnpackParams &p, uint32_t cus, hipStream_t s)
-{
-    const uint64_t groups = ((uint64_t)p.n + (64 / G) - 1) / (64 / G);
-    const uint64_t blocks = (groups + (kUnpackBlock / 64) - 1) / (kUnpackBlock / 64);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1u) * kUnpackBlocksPerCU);
-    hipLaunchKernelGGL(k_unpack<G>, dim3(grid), dim3(kUnpackBlock), 0, s, p);
-    return hipGetLastError();
+    return launch_at_lanes(l.lanes, "k_pack launch", [&](auto G) {
+        hipLaunchKernelGGL(k_pack<decltype(G)::value>, dim3(l.grid), dim3(kBlock), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 // Workspace of val_frame_unpack_batch_dev for n frames: dst and the parsed
 // offsets (u64), the payload states and lengths (u32), the verdicts (u8).
-uint64_t unpack_work_bytes(uint32_t n) { return ((uint64_t)n * 25u + 15u) & ~(uint64_t)15; }
+// The verify launches write two of the regions and the unpack kernels read
+// them, so the regions come typed; bytes is their size.
+struct UnpackWork {
+    uint64_t *dst, *foff;
+    uint32_t *pay, *plen;
+    uint8_t *ok;
+    uint64_t bytes;
+    UnpackWork(void *d_work, uint32_t n)
+    {
+        Carve w{(uintptr_t)d_work};
+        dst = w.take<uint64_t>(n);
+        foff = w.take<uint64_t>(n);
+        pay = w.take<uint32_t>(n);
+        plen = w.take<uint32_t>(n);
+        ok = w.take<uint8_t>(n);
+        bytes = (w.used + 15u) & ~(uint64_t)15;
+    }
+};
+
+// The checks both unpack calls open with.
+val_status_t unpack_checks(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const void *d_work,
+                           uint64_t work_bytes)
+{
+    const val_status_t st = check_off_len(d_off, d_len);
+    if (st != VAL_OK) return st;
+    return check_work(d_work, work_bytes, val_frame_unpack_work_bytes(n),
+                      "work_bytes below val_frame_unpack_work_bytes(n)");
+}
 
 // The launches of both unpack calls on stream s: `u` holds the file side (one
 // file, or with `files` the per-file arrays); the frames, the workspace and
@@ -1712,98 +1761,77 @@ val_status_t unpack_launch(Ctx &c, UnpackParams &u, bool files, const uint8_t *d
                            const uint32_t *d_len, uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint,
                            uint8_t *d_ok, uint32_t *d_nbad, uint8_t *d_accept, void *d_work, hipStream_t s)
 {
-    uint8_t *w = (uint8_t *)d_work;
+    const UnpackWork w(d_work, n);
+    uint8_t *ok = d_ok ? d_ok : w.ok;
     u.base = d_base;
     u.off = d_off;
     u.len = d_len;
     u.stride = stride;
     u.flen = flen;
     u.n = n;
-    u.dst = (uint64_t *)w;
-    u.foff = (uint64_t *)(w + (uint64_t)n * 8u);
-    uint32_t *pay = (uint32_t *)(w + (uint64_t)n * 16u);
-    u.pay = pay;
-    u.plen = (uint32_t *)(w + (uint64_t)n * 20u);
-    uint8_t *ok = d_ok ? d_ok : w + (uint64_t)n * 24u;
+    u.dst = w.dst;
+    u.foff = w.foff;
+    u.pay = w.pay;
+    u.plen = w.plen;
     u.ok = ok;
     u.accept = d_accept;
     u.consts = c.d_consts;
     // 1. verify: the launches of val_crc32_verify_frames_ex_dev
-    FrameParams p{};
-    p.base = d_base;
-    p.off = d_off;
-    p.len = d_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
+    FrameParams p = data_frames(d_base, d_off, d_len, stride, flen, n);
     p.verify = 1;
     p.out_ok = ok;
     p.nbad = d_nbad;
-    p.out_pay = pay;
+    p.out_pay = w.pay;
     const uint32_t typical_len = d_off ? len_hint : flen;
     val_status_t st = launch_frames(c, p, typical_len, s);
     if (st != VAL_OK) return st;
-    // 2. order: header facts grid-wide, then the receiver's rule: one workgroup for one file,
-    // else a workgroup per file up to one per CU
-    const dim3 pgrid((uint32_t)(((uint64_t)n + 255u) / 256u));
-    if (files) hipLaunchKernelGGL(k_unpack_parse<true>, pgrid, dim3(256), 0, s, u);
-    else hipLaunchKernelGGL(k_unpack_parse<false>, pgrid, dim3(256), 0, s, u);
+    // 2. order: the header facts, then the receiver's rule; 3. scatter
+    const WindowPlan plan = plan_unpack((uint32_t)c.cus, n, files, u.n_files, typical_len, plan_knobs());
+    const Launch &parse = plan.launch[0], &order = plan.launch[1], &scatter = plan.launch[2];
+    if (files) hipLaunchKernelGGL(k_unpack_parse<true>, dim3(parse.grid), dim3(256), 0, s, u);
+    else hipLaunchKernelGGL(k_unpack_parse<false>, dim3(parse.grid), dim3(256), 0, s, u);
     VCRC_HIP(hipGetLastError(), "k_unpack_parse launch");
-    if (files) {
-        const uint32_t ogrid = std::min(u.n_files, (uint32_t)std::max(c.cus, 1));
-        hipLaunchKernelGGL(k_unpack_order_files, dim3(ogrid), dim3(kOrderBlock), 0, s, u);
-    } else {
-        hipLaunchKernelGGL(k_unpack_order, dim3(1), dim3(kOrderBlock), 0, s, u);
-    }
+    if (files) hipLaunchKernelGGL(k_unpack_order_files, dim3(order.grid), dim3(kOrderBlock), 0, s, u);
+    else hipLaunchKernelGGL(k_unpack_order, dim3(order.grid), dim3(kOrderBlock), 0, s, u);
     VCRC_HIP(hipGetLastError(), "k_unpack_order launch");
-    // 3. scatter
-    uint32_t lanes = forced_lanes();
-    if (!lanes) {
-        lanes = val_gpu_lanes_per_frame(typical_len ? typical_len : 1100u);
-        // as k_pack: a batch that leaves workgroups of the grid empty doubles its lanes until it fills them
-        const uint64_t threads = (uint64_t)std::max(c.cus, 1) * kUnpackBlocksPerCU * kUnpackBlock;
-        while (lanes < 64u && (uint64_t)n * lanes * 2u <= threads) lanes *= 2u;
-    }
-    hipError_t e = hipErrorInvalidValue;
-    switch (lanes) {
-    case 1: e = launch_k_unpack<1>(u, (uint32_t)c.cus, s); break;
-    case 2: e = launch_k_unpack<2>(u, (uint32_t)c.cus, s); break;
-    case 4: e = launch_k_unpack<4>(u, (uint32_t)c.cus, s); break;
-    case 8: e = launch_k_unpack<8>(u, (uint32_t)c.cus, s); break;
-    case 16: e = launch_k_unpack<16>(u, (uint32_t)c.cus, s); break;
-    case 32: e = launch_k_unpack<32>(u, (uint32_t)c.cus, s); break;
-    case 64: e = launch_k_unpack<64>(u, (uint32_t)c.cus, s); break;
-    default: return fail(VAL_ERR_INVALID_ARG, "bad lanes-per-frame");
-    }
-    VCRC_HIP(e, "k_unpack launch");
-    return VAL_OK;
+    return launch_at_lanes(scatter.lanes, "k_unpack launch", [&](auto G) {
+        hipLaunchKernelGGL(k_unpack<decltype(G)::value>, dim3(scatter.grid), dim3(kUnpackBlock), 0, s, u);
+        return hipGetLastError();
+    });
 }
 
 // Workspace of val_frame_scan_streams_dev: every stream's slot of max_frames
 // descriptors (u64 offset, u32 length) and the streams' counts (u32). A
 // product beyond 32 bits, which the call refuses, asks for more than any
-// buffer holds.
-std::atomic<uint32_t> g_scan_front{0};  // val_gpu_set_scan_front: 0 = by the number of streams
-
-uint64_t scan_work_bytes(uint32_t n_streams, uint32_t max_frames)
+// buffer holds. scan_work and fill_work place the regions of d_work in the
+// params and return their size.
+uint64_t scan_work(uint32_t n_streams, uint32_t max_frames, void *d_work, ScanParams &p)
 {
     const uint64_t slots = (uint64_t)n_streams * max_frames;
     if (slots > UINT32_MAX) return ~(uint64_t)7;
-    return (slots * 12u + (uint64_t)n_streams * 4u + 7u) & ~(uint64_t)7;
+    Carve w{(uintptr_t)d_work};
+    p.woff = w.take<uint64_t>(slots);
+    p.wlen = w.take<uint32_t>(slots);
+    p.wcnt = w.take<uint32_t>(n_streams);
+    return (w.used + 7u) & ~(uint64_t)7;
 }
 
 // Workspace of val_frame_fill_files_dev: k_pack's inputs for every slot (u64
 // payload and file offsets, u32 payload length, u8 explicit flag), and per
 // transfer its position before the call (u64) and its count (u32). A product
 // beyond 32 bits, which the call refuses, asks for more than any buffer holds.
-uint64_t fill_work_bytes(uint32_t n_files, uint32_t max_frames)
+uint64_t fill_work(uint32_t n_files, uint32_t max_frames, void *d_work, FillParams &f)
 {
     const uint64_t slots = (uint64_t)n_files * max_frames;
     if (slots > UINT32_MAX) return ~(uint64_t)7;
-    return (slots * 21u + (uint64_t)n_files * 12u + 7u) & ~(uint64_t)7;
+    Carve w{(uintptr_t)d_work};
+    f.wpay_off = w.take<uint64_t>(slots);
+    f.wfile_off = w.take<uint64_t>(slots);
+    f.wnext = w.take<uint64_t>(n_files);
+    f.wpay_len = w.take<uint32_t>(slots);
+    f.wcnt = w.take<uint32_t>(n_files);
+    f.wexpl = w.take<uint8_t>(slots);
+    return (w.used + 7u) & ~(uint64_t)7;
 }
 
 }  // namespace vcrc
@@ -2063,6 +2091,22 @@ uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t
     return plan.count;
 }
 
+uint32_t val_gpu_plan_window(uint32_t call, uint32_t cus, uint32_t n, uint32_t groups, uint32_t max_frames,
+                             uint32_t len_hint, val_gpu_launch_t out[4])
+{
+    WindowPlan plan;
+    switch (call) {
+    case VAL_GPU_WINDOW_PACK: plan = plan_pack(cus, n, len_hint, plan_knobs()); break;
+    case VAL_GPU_WINDOW_UNPACK: plan = plan_unpack(cus, n, false, 0, len_hint, plan_knobs()); break;
+    case VAL_GPU_WINDOW_UNPACK_FILES: plan = plan_unpack(cus, n, true, groups, len_hint, plan_knobs()); break;
+    case VAL_GPU_WINDOW_SCAN: plan = plan_scan(cus, n, max_frames, plan_knobs()); break;
+    case VAL_GPU_WINDOW_FILL: plan = plan_fill(cus, n, max_frames, len_hint, plan_knobs()); break;
+    default: break;
+    }
+    for (uint32_t i = 0; out && i < plan.count; i++) out[i] = plan.launch[i];
+    return plan.count;
+}
+
 val_status_t val_gpu_set_lanes_per_frame(uint32_t lanes)
 {
     if (lanes != 0 && !valid_lanes(lanes)) return fail(VAL_ERR_INVALID_ARG, "lanes must be 0 or a power of two <= 64");
@@ -2153,22 +2197,13 @@ static val_status_t frames_dev(const uint8_t *d_base, const uint64_t *d_off, con
                                uint32_t *d_nbad, uint32_t *d_crc, uint32_t *d_hdr, uint32_t *d_pay, void *stream)
 {
     t_err.clear();
-    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
+    val_status_t st = check_off_len(d_off, d_len);
+    if (st != VAL_OK) return st;
     if (!d_base && n) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
     DeviceScope ds;
     Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_base, &c);
-    if (st != VAL_OK) return st;
-    FrameParams p{};
-    p.base = d_base;
-    p.off = d_off;
-    p.len = d_len;
-    p.stride = stride;
-    p.flen = flen;
-    p.last_len = flen;
-    p.n = n;
-    p.seed0 = p.seed_rest = 0xFFFFFFFFu;
-    p.xorout = 0xFFFFFFFFu;
+    if ((st = cur_dev(stream, d_base, &c)) != VAL_OK) return st;
+    FrameParams p = data_frames(d_base, d_off, d_len, stride, flen, n);
     p.out_crc = d_crc;
     p.out_hdr = d_hdr;
     p.verify = verify;
@@ -2222,10 +2257,10 @@ val_status_t val_frame_data_batch_dev(const uint8_t *d_payload, const uint64_t *
     p.out_hdr = d_hdr;
     p.nrejected = d_nrejected;
     p.consts = c->d_consts;
-    return pack_launch(*c, p, len_hint, pick_stream(stream));
+    return pack_launch(p, plan_pack((uint32_t)c->cus, n, len_hint, plan_knobs()).launch[0], pick_stream(stream));
 }
 
-uint64_t val_frame_unpack_work_bytes(uint32_t n) { return unpack_work_bytes(n); }
+uint64_t val_frame_unpack_work_bytes(uint32_t n) { return UnpackWork(nullptr, n).bytes; }
 
 val_status_t val_frame_unpack_batch_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
                                         uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint, uint8_t *d_file,
@@ -2234,17 +2269,14 @@ val_status_t val_frame_unpack_batch_dev(const uint8_t *d_base, const uint64_t *d
                                         uint32_t *d_noverflow, void *d_work, uint64_t work_bytes, void *stream)
 {
     t_err.clear();
-    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
-    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
-    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
-    if (work_bytes < unpack_work_bytes(n)) return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_unpack_work_bytes(n)");
+    val_status_t st = unpack_checks(d_off, d_len, n, d_work, work_bytes);
+    if (st != VAL_OK) return st;
     if (n == 0) return VAL_OK;
     if (!d_file || !d_written) return fail(VAL_ERR_INVALID_ARG, "file or written is NULL");
     if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
     DeviceScope ds;
     Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_file, &c);
-    if (st != VAL_OK) return st;
+    if ((st = cur_dev(stream, d_file, &c)) != VAL_OK) return st;
     UnpackParams u{};
     u.file = d_file;
     u.file_cap = file_cap;
@@ -2264,10 +2296,8 @@ val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d
                                         uint8_t *d_accept, void *d_work, uint64_t work_bytes, void *stream)
 {
     t_err.clear();
-    if ((d_off == nullptr) != (d_len == nullptr)) return fail(VAL_ERR_INVALID_ARG, "off/len must both be set or both NULL");
-    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
-    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
-    if (work_bytes < unpack_work_bytes(n)) return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_unpack_work_bytes(n)");
+    val_status_t st = unpack_checks(d_off, d_len, n, d_work, work_bytes);
+    if (st != VAL_OK) return st;
     if (n == 0 || n_files == 0) return VAL_OK;
     if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
     if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
@@ -2276,8 +2306,7 @@ val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d
     if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
     DeviceScope ds;
     Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_written, &c);
-    if (st != VAL_OK) return st;
+    if ((st = cur_dev(stream, d_written, &c)) != VAL_OK) return st;
     UnpackParams u{};
     u.n_files = n_files;
     u.first = d_first;
@@ -2302,7 +2331,8 @@ val_status_t val_gpu_set_scan_front(uint32_t lanes)
 
 uint64_t val_frame_scan_work_bytes(uint32_t n_streams, uint32_t max_frames)
 {
-    return scan_work_bytes(n_streams, max_frames);
+    ScanParams p{};
+    return scan_work(n_streams, max_frames, nullptr, p);
 }
 
 val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d_stream_off,
@@ -2313,12 +2343,12 @@ val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d
 {
     t_err.clear();
     if (mtu < VAL_WIRE_HEADER_SIZE + VAL_WIRE_TRAILER_SIZE) return fail(VAL_ERR_INVALID_ARG, "mtu below 12");
-    const uint64_t slots = (uint64_t)n_streams * max_frames;
-    if (slots > UINT32_MAX) return fail(VAL_ERR_INVALID_ARG, "n_streams * max_frames overflows 32 bits");
-    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
-    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
-    if (work_bytes < scan_work_bytes(n_streams, max_frames))
-        return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_scan_work_bytes(n_streams, max_frames)");
+    val_status_t st = check_slots(n_streams, max_frames, "n_streams * max_frames overflows 32 bits");
+    if (st != VAL_OK) return st;
+    ScanParams p{};
+    if ((st = check_work(d_work, work_bytes, scan_work(n_streams, max_frames, d_work, p),
+                         "work_bytes below val_frame_scan_work_bytes(n_streams, max_frames)")) != VAL_OK)
+        return st;
     if (n_streams == 0) return VAL_OK;
     if (max_frames > 0) {
         if (!d_stream_off) return fail(VAL_ERR_INVALID_ARG, "stream_off is NULL");
@@ -2330,59 +2360,42 @@ val_status_t val_frame_scan_streams_dev(const uint8_t *d_base, const uint64_t *d
     }
     DeviceScope ds;
     Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_base, &c);
-    if (st != VAL_OK) return st;
+    if ((st = cur_dev(stream, d_base, &c)) != VAL_OK) return st;
     const hipStream_t s = pick_stream(stream);
     if (max_frames == 0) {  // no stream is looked at: every count, consumed and status (VAL_OK) is 0
-        if (d_first) VCRC_HIP(hipMemsetAsync(d_first, 0, ((size_t)n_streams + 1u) * 4u, s), "memset(first)");
-        if (d_nframes) VCRC_HIP(hipMemsetAsync(d_nframes, 0, (size_t)n_streams * 4u, s), "memset(nframes)");
-        if (d_consumed) VCRC_HIP(hipMemsetAsync(d_consumed, 0, (size_t)n_streams * 8u, s), "memset(consumed)");
+        if ((st = zero_window_outputs(n_streams, d_first, d_nframes, d_consumed, "memset(consumed)", s)) != VAL_OK)
+            return st;
         if (d_status) VCRC_HIP(hipMemsetAsync(d_status, 0, (size_t)n_streams * 4u, s), "memset(status)");
         return VAL_OK;
     }
-    uint8_t *w = (uint8_t *)d_work;
-    ScanParams p{};
     p.base = d_base;
     p.stream_off = d_stream_off;
     p.stream_len = d_stream_len;
     p.n_streams = n_streams;
     p.max_frames = max_frames;
     p.max_content = mtu - VAL_WIRE_HEADER_SIZE - VAL_WIRE_TRAILER_SIZE;
-    p.woff = (uint64_t *)w;
-    p.wlen = (uint32_t *)(w + slots * 8u);
-    p.wcnt = (uint32_t *)(w + slots * 12u);
     p.frame_off = d_frame_off;
     p.crc_len = d_crc_len;
     p.first = d_first;
     p.nframes = d_nframes;
     p.consumed = d_consumed;
     p.status = d_status;
-    // The walk, in a persistent grid: a workgroup of 16 waves per stream while every stream can
-    // have a CU of its own, else a wave per stream. Results do not depend on it.
-    const uint64_t cus = (uint64_t)std::max(c->cus, 1);
-    const uint64_t cap = cus * kScanBlocksPerCU;
-    uint32_t front = g_scan_front.load(std::memory_order_relaxed);
-    if (!front) front = n_streams <= cus ? 64u * kScanWideWaves : 64u;
-    if (front == 64u) {
-        constexpr uint32_t per = kScanBlock / 64;
-        const uint32_t wgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n_streams + per - 1) / per, cap);
-        hipLaunchKernelGGL(k_scan_streams<1>, dim3(wgrid), dim3(kScanBlock), 0, s, p);
-    } else {
-        const uint32_t wgrid = (uint32_t)std::min<uint64_t>(n_streams, cus * 2u);
-        hipLaunchKernelGGL(k_scan_streams<kScanWideWaves>, dim3(wgrid), dim3(64 * kScanWideWaves), 0, s, p);
-    }
+    const WindowPlan plan = plan_scan((uint32_t)c->cus, n_streams, max_frames, plan_knobs());
+    const Launch &walk = plan.launch[0], &first = plan.launch[1], &compact = plan.launch[2];
+    if (walk.lanes == 64u) hipLaunchKernelGGL(k_scan_streams<1>, dim3(walk.grid), dim3(kScanBlock), 0, s, p);
+    else hipLaunchKernelGGL(k_scan_streams<kScanWideWaves>, dim3(walk.grid), dim3(64 * kScanWideWaves), 0, s, p);
     VCRC_HIP(hipGetLastError(), "k_scan_streams launch");
-    hipLaunchKernelGGL(k_scan_first, dim3(1), dim3(kScanFirstBlock), 0, s, p);
+    hipLaunchKernelGGL(k_scan_first, dim3(first.grid), dim3(kScanFirstBlock), 0, s, p);
     VCRC_HIP(hipGetLastError(), "k_scan_first launch");
-    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((slots + kScanBlock - 1) / kScanBlock, cap);
-    hipLaunchKernelGGL(k_scan_compact, dim3(cgrid), dim3(kScanBlock), 0, s, p);
+    hipLaunchKernelGGL(k_scan_compact, dim3(compact.grid), dim3(kScanBlock), 0, s, p);
     VCRC_HIP(hipGetLastError(), "k_scan_compact launch");
     return VAL_OK;
 }
 
 uint64_t val_frame_fill_work_bytes(uint32_t n_files, uint32_t max_frames)
 {
-    return fill_work_bytes(n_files, max_frames);
+    FillParams f{};
+    return fill_work(n_files, max_frames, nullptr, f);
 }
 
 val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *d_file_pos,
@@ -2396,12 +2409,12 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
     t_err.clear();
     if (mtu < VAL_FILL_MTU_MIN) return fail(VAL_ERR_INVALID_ARG, "mtu below 21");
     if (mtu > VAL_FILL_MTU_MAX) return fail(VAL_ERR_INVALID_ARG, "mtu above 65547");
-    const uint64_t slots = (uint64_t)n_files * max_frames;
-    if (slots > UINT32_MAX) return fail(VAL_ERR_INVALID_ARG, "n_files * max_frames overflows 32 bits");
-    if (!d_work) return fail(VAL_ERR_INVALID_ARG, "work is NULL");
-    if (((uintptr_t)d_work & 7u) != 0) return fail(VAL_ERR_INVALID_ARG, "work is not 8-byte aligned");
-    if (work_bytes < fill_work_bytes(n_files, max_frames))
-        return fail(VAL_ERR_INVALID_ARG, "work_bytes below val_frame_fill_work_bytes(n_files, max_frames)");
+    val_status_t st = check_slots(n_files, max_frames, "n_files * max_frames overflows 32 bits");
+    if (st != VAL_OK) return st;
+    FillParams f{};
+    if ((st = check_work(d_work, work_bytes, fill_work(n_files, max_frames, d_work, f),
+                         "work_bytes below val_frame_fill_work_bytes(n_files, max_frames)")) != VAL_OK)
+        return st;
     if (n_files == 0) return VAL_OK;
     if (max_frames > 0) {
         if (!d_payload) return fail(VAL_ERR_INVALID_ARG, "payload is NULL");
@@ -2417,17 +2430,10 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
     }
     DeviceScope ds;
     Ctx *c = nullptr;
-    val_status_t st = cur_dev(stream, d_out, &c);
-    if (st != VAL_OK) return st;
+    if ((st = cur_dev(stream, d_out, &c)) != VAL_OK) return st;
     const hipStream_t s = pick_stream(stream);
-    if (max_frames == 0) {  // no transfer is looked at: every count and length is 0, next stays
-        if (d_first) VCRC_HIP(hipMemsetAsync(d_first, 0, ((size_t)n_files + 1u) * 4u, s), "memset(first)");
-        if (d_nframes) VCRC_HIP(hipMemsetAsync(d_nframes, 0, (size_t)n_files * 4u, s), "memset(nframes)");
-        if (d_stream_len) VCRC_HIP(hipMemsetAsync(d_stream_len, 0, (size_t)n_files * 8u, s), "memset(stream_len)");
-        return VAL_OK;
-    }
-    uint8_t *w = (uint8_t *)d_work;
-    FillParams f{};
+    // max_frames == 0: no transfer is looked at: every count and length is 0, next stays
+    if (max_frames == 0) return zero_window_outputs(n_files, d_first, d_nframes, d_stream_len, "memset(stream_len)", s);
     f.file_pos = d_file_pos;
     f.file_size = d_file_size;
     f.next = d_next;
@@ -2442,27 +2448,20 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
     f.nframes = d_nframes;
     f.first = d_first;
     f.frame_off = d_frame_off;
-    f.wpay_off = (uint64_t *)w;
-    f.wfile_off = (uint64_t *)(w + slots * 8u);
-    f.wnext = (uint64_t *)(w + slots * 16u);
-    f.wpay_len = (uint32_t *)(w + slots * 16u + (uint64_t)n_files * 8u);
-    f.wcnt = (uint32_t *)(w + slots * 20u + (uint64_t)n_files * 8u);
-    f.wexpl = w + slots * 20u + (uint64_t)n_files * 12u;
+    const WindowPlan plan = plan_fill((uint32_t)c->cus, n_files, max_frames, mtu, plan_knobs());
+    const Launch &count = plan.launch[0], &first = plan.launch[1], &desc = plan.launch[2], &pack = plan.launch[3];
     // 1. the counts, the streams' lengths and the new positions
-    const uint32_t ngrid = (uint32_t)(((uint64_t)n_files + kFillBlock - 1) / kFillBlock);
-    hipLaunchKernelGGL(k_fill_count, dim3(ngrid), dim3(kFillBlock), 0, s, f);
+    hipLaunchKernelGGL(k_fill_count, dim3(count.grid), dim3(kFillBlock), 0, s, f);
     VCRC_HIP(hipGetLastError(), "k_fill_count launch");
     // 2. d_first: the scan call's kernel over this call's counts
     ScanParams sp{};
     sp.n_streams = n_files;
     sp.wcnt = f.wcnt;
     sp.first = d_first;
-    hipLaunchKernelGGL(k_scan_first, dim3(1), dim3(kScanFirstBlock), 0, s, sp);
+    hipLaunchKernelGGL(k_scan_first, dim3(first.grid), dim3(kScanFirstBlock), 0, s, sp);
     VCRC_HIP(hipGetLastError(), "k_scan_first launch");
     // 3. k_pack's inputs, compacted in transfer order, the rest padded with rejects
-    const uint64_t cap = (uint64_t)std::max(c->cus, 1) * kFillBlocksPerCU;
-    const uint32_t dgrid = (uint32_t)std::min<uint64_t>((slots + kFillBlock - 1) / kFillBlock, cap);
-    hipLaunchKernelGGL(k_fill_desc, dim3(dgrid), dim3(kFillBlock), 0, s, f);
+    hipLaunchKernelGGL(k_fill_desc, dim3(desc.grid), dim3(kFillBlock), 0, s, f);
     VCRC_HIP(hipGetLastError(), "k_fill_desc launch");
     // 4. the frames: k_pack over every entry; a padding entry writes nothing and zeroes its outputs
     PackParams p{};
@@ -2471,14 +2470,14 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
     p.pay_len = f.wpay_len;
     p.file_off = f.wfile_off;
     p.include_offset = f.wexpl;
-    p.n = (uint32_t)slots;
+    p.n = pack.count;
     p.out = d_out;
     p.frame_off = d_frame_off;
     p.out_len = d_crc_len;
     p.out_crc = d_crc;
     p.out_hdr = d_hdr;
     p.consts = c->d_consts;
-    return pack_launch(*c, p, (uint32_t)(mtu - VAL_WIRE_TRAILER_SIZE), s);
+    return pack_launch(p, pack, s);
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

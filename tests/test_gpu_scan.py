@@ -46,7 +46,7 @@ def _host(wire, stream, mtu, max_frames):
     return wire.scan_frames(stream, mtu, max_frames)
 
 
-def _scan(vc, wire, streams, mtu, max_frames, *, phases=(0, 1, 2, 3), null=()):
+def _scan(vc, wire, streams, mtu, max_frames, *, phases=(0, 1, 2, 3), null=(), fronts=FRONTS):
     """streams: list of (bytes, len) or plain byte arrays; the stream is bytes[:len] and bytes[len:]
     follows it in the buffer. The whole list is laid out once per phase shift, so every stream starts
     at every phase of phases. -> the per-stream host results of the first copy."""
@@ -77,7 +77,7 @@ def _scan(vc, wire, streams, mtu, max_frames, *, phases=(0, 1, 2, 3), null=()):
     w_first = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
     w_off = np.concatenate([w[1] + soff[s] for s, w in enumerate(want)] + [np.zeros(slots - total, np.uint64)])
     w_len = np.concatenate([w[2] for w in want] + [np.zeros(slots - total, np.uint32)])
-    for front in FRONTS:  # automatic, then each instantiation of the walk: the results are the same
+    for front in fronts:  # automatic, then each instantiation of the walk: the results are the same
         foff = torch.full((slots + PAD,), C64, dtype=torch.int64, device=DEV)
         clen = torch.full((slots + PAD,), C32, dtype=torch.int32, device=DEV)
         first = torch.full((S + 1 + PAD,), C32, dtype=torch.int32, device=DEV)
@@ -137,8 +137,12 @@ def test_no_runs(vc, wire):
 
 @pytest.mark.parametrize("run", [63, 64, 65, 255, 256, 257, 1023, 1024, 1025])
 def test_front_width_boundaries(vc, wire, run):
-    """A run that ends one frame before, at and one frame behind a front of 64, 256 and 1,024
-    lanes, then a frame of another size, then the run's size again."""
+    """A run of 64 k - 1, 64 k and 64 k + 1 frames (k = 1, 4, 16), then a frame of another size,
+    then the run's size again. For the one-wave walk, whose rounds end at frames 1 + 64 k, the
+    runs of 64 k + 1 end on a round and the others one and two frames before it. The wide front
+    looks with 64, 256 and 1,024 lanes in turn, so its rounds end at frames 1, 65, 321 and 1,345:
+    of these only 65 is a run here, and no run is long enough for a round in which all 1,024
+    lanes match. Those edges are in test_gpu_window_edges.py."""
     content = run % 5  # wire 12 .. 16
     other = (content + 2) % 5
     s = _cat([_f(wire, content)] * run + [_f(wire, other)] + [_f(wire, content)] * 3)

@@ -418,6 +418,125 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
                                       uint64_t *d_frame_off, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
                                       void *d_work, uint64_t work_bytes, void *stream);
 
+/* CRC-32 of one byte window of each of n_files GPU-resident files, in one
+ * device call: the many-files form of val_crc32_region_dev, for callers whose
+ * file sizes and windows exist only in HBM (a receiver that has just delivered
+ * a window with val_frame_unpack_files_dev has its files' sizes in d_written).
+ * Async on `stream`; all pointers are device pointers; nothing is synchronised
+ * and no library scratch is kept: the per-file accumulators and arrival counts
+ * live in the caller's d_work.
+ * For each file s, d_crc[s] is the finalized CRC-32 (seed 0xFFFFFFFF, final
+ * XOR: what the reference's val_internal_crc32_region returns) of bytes
+ * [d_win_off[s], d_win_off[s] + d_win_len[s]) of the file of d_file_size[s]
+ * bytes whose byte 0 is at device address d_file_ptr[s]; an empty window
+ * gives 0. Window starts and ends have any byte alignment.
+ * Windows are made safe, not trusted: a window with
+ * d_win_off[s] + d_win_len[s] > d_file_size[s] (judged without 64-bit
+ * wrap-around) or d_win_len[s] > max_len gets d_status[s] =
+ * VAL_ERR_INVALID_ARG and d_crc[s] = 0, and no byte of it is read; every
+ * other file gets d_status[s] = VAL_OK (d_status nullable). That a file's
+ * d_file_size bytes at d_file_ptr are readable is the caller's promise.
+ * max_len is the caller's bound on any window and fixes the geometry on the
+ * host: 0 .. 2^32 (a VERIFY request carries 32 bits). max_len == 0 is valid:
+ * only empty windows are VAL_OK.
+ * Reads: only aligned dwords that overlap an accepted window are read from a
+ * file (whole 64-byte units inside it, its first and last dwords, or, for a
+ * window of fewer than 4 bytes, those bytes); nothing is written but the
+ * outputs and d_work.
+ * It is a short pipeline on the stream: a count
+ * launch of one thread per file that validates the window and counts its
+ * chunks, the prefix sum, and a hash launch in a persistent grid over all
+ * chunks of all files, so one long window among many short ones still spreads
+ * over the machine. The chunk size is one for the call, 2^k0 bytes with k0 in
+ * 12..16, chosen from max_len and n_files (val_gpu_plan_file_windows shows it;
+ * val_gpu_set_file_window_chunk forces it). Chunk states are folded into the
+ * file's accumulator with device-scope atomics; the last chunk of a file to
+ * arrive writes its outputs; no workgroup waits for another, and the result is
+ * bit-exact whatever the arrival order.
+ * d_work: val_file_windows_work_bytes(n_files) bytes, 8-byte aligned. The call
+ * zeroes what it needs itself: the contents on entry are unspecified, as they
+ * are after the call, and calls on one stream may share one d_work. It must
+ * not overlap the inputs or the outputs.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when d_work is NULL or misaligned, work_bytes is below
+ * val_file_windows_work_bytes(n_files), max_len is above 2^32, n_files times
+ * the chunks of a max_len window (at 64 KiB chunks) overflows 32 bits, and,
+ * with n_files > 0, when d_file_ptr, d_file_size, d_win_off, d_win_len or
+ * d_crc is NULL. Otherwise n_files == 0 returns VAL_OK and launches nothing.
+ * The call runs on the stream's device (else the device d_work lives on). */
+uint64_t val_file_windows_work_bytes(uint32_t n_files);
+val_status_t val_crc32_file_windows_dev(const uint64_t *d_file_ptr, const uint64_t *d_file_size,
+                                        const uint64_t *d_win_off, const uint64_t *d_win_len, uint32_t n_files,
+                                        uint64_t max_len, uint32_t *d_crc, int32_t *d_status,
+                                        void *d_work, uint64_t work_bytes, void *stream);
+
+/* The VAL_RESUME_TAIL handshake of n_files GPU-resident files, three calls
+ * thin over that pipeline: each is the count launch with one of the rules of
+ * val_wire.h applied per file, the prefix sum, the hash launch, and the finish
+ * in the last chunk to arrive. They share val_crc32_file_windows_dev's
+ * addressing (d_file_ptr), workspace (val_file_windows_work_bytes(n_files)),
+ * read guarantee, stream and device semantics, and its argument checks: d_work
+ * and work_bytes, max_len, the chunk product, and with n_files > 0 every
+ * pointer not called nullable below; n_files == 0 returns VAL_OK and launches
+ * nothing. Actions are val_resume_action_t values and results val_status_t
+ * values, both as int32.
+ *
+ * val_resume_tail_files_dev, the receiver's proposal: per file
+ * val_resume_tail_window(d_existing[s], d_incoming[s], tail_cap_bytes,
+ * min_verify_bytes, mismatch_skip) gives d_action[s], d_resume_off[s] and
+ * d_verify_len[s]; for VAL_RESUME_VERIFY_FIRST files d_verify_crc[s] is the
+ * CRC of the last d_verify_len[s] bytes of the local file of d_existing[s]
+ * bytes, and 0 for every other action. d_existing can be the d_written of
+ * val_frame_unpack_files_dev on the same stream, with no read-back. max_len is
+ * derived on the host, max(the clamped cap, min_verify_bytes); a
+ * min_verify_bytes above 2^32 is refused. All outputs are required.
+ *
+ * val_resume_request_files_dev, the sender's answer, over its own copies of
+ * the files: for files with d_action[s] == VAL_RESUME_VERIFY_FIRST for which
+ * val_resume_request_window(d_resume_off[s], d_verify_len[s]) gives a
+ * non-empty window, d_req_off[s] and d_req_len[s] are that window and
+ * d_req_crc[s] its CRC in the file of d_file_size[s] bytes; d_status[s]
+ * (nullable) is as in the generic call (a window outside the file or above
+ * max_len: VAL_ERR_INVALID_ARG and d_req_crc[s] = 0). For every other file
+ * d_req_off[s] = d_resume_off[s], d_req_len[s] = d_req_crc[s] = 0,
+ * d_status[s] = VAL_OK, and nothing is read.
+ *
+ * val_resume_check_files_dev, the receiver's check of the VERIFY request: for
+ * files with d_action[s] == VAL_RESUME_VERIFY_FIRST (d_action NULL: every
+ * file), the CRC of [d_req_off[s], d_req_off[s] + d_req_len[s]) of the local
+ * file of d_existing[s] bytes goes to d_local_crc[s] (nullable; what the
+ * VERIFY response carries), and val_resume_verdict(window_ok, that CRC,
+ * d_req_crc[s], mismatch_skip, d_rec_resume_off[s], d_incoming[s]) gives
+ * d_result[s] and d_written[s], the offset the transfer resumes at. window_ok
+ * is 0 when the window does not lie inside the local file or exceeds max_len;
+ * then nothing is read and d_local_crc[s] = 0. Files with any other action are
+ * left untouched in every output. d_written then feeds the next
+ * val_frame_unpack_files_dev call unchanged, and d_next / d_last_acked of a
+ * val_frame_fill_files_dev call on the peer.
+ *
+ * Out of scope: the rolling d_file_state of a resumed file (it needs the CRC
+ * of the whole prefix, not of a window: val_crc32_file_windows_dev with the
+ * window [0, d_written[s]) gives its finalized form); the NEVER and
+ * SKIP_EXISTING modes, which hash nothing; and building or parsing the
+ * RESUME_RESP and VERIFY control frames, whose codecs exist on the host
+ * (val_wire.h). */
+val_status_t val_resume_tail_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_existing,
+                                       const uint64_t *d_incoming, uint32_t n_files, uint64_t tail_cap_bytes,
+                                       uint64_t min_verify_bytes, int mismatch_skip, int32_t *d_action,
+                                       uint64_t *d_resume_off, uint64_t *d_verify_len, uint32_t *d_verify_crc,
+                                       void *d_work, uint64_t work_bytes, void *stream);
+val_status_t val_resume_request_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_file_size,
+                                          const int32_t *d_action, const uint64_t *d_resume_off,
+                                          const uint64_t *d_verify_len, uint32_t n_files, uint64_t max_len,
+                                          uint64_t *d_req_off, uint32_t *d_req_len, uint32_t *d_req_crc,
+                                          int32_t *d_status, void *d_work, uint64_t work_bytes, void *stream);
+val_status_t val_resume_check_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_existing,
+                                        const uint64_t *d_incoming, const int32_t *d_action,
+                                        const uint64_t *d_req_off, const uint32_t *d_req_len,
+                                        const uint32_t *d_req_crc, const uint64_t *d_rec_resume_off, uint32_t n_files,
+                                        uint64_t max_len, int mismatch_skip, uint32_t *d_local_crc, int32_t *d_result,
+                                        uint64_t *d_written, void *d_work, uint64_t work_bytes, void *stream);
+
 /* Region CRC of one long device buffer: *d_state_out = raw register after
  * feeding d_ptr[0, len) to `state_in` (val_crc32_update_state semantics;
  * finalize with ^0xFFFFFFFF). One launch at any length: windows up to 8
@@ -600,7 +719,10 @@ enum {
     VAL_GPU_KERNEL_SCAN_FIRST = 10,
     VAL_GPU_KERNEL_SCAN_COMPACT = 11,
     VAL_GPU_KERNEL_FILL_COUNT = 12,
-    VAL_GPU_KERNEL_FILL_DESC = 13
+    VAL_GPU_KERNEL_FILL_DESC = 13,
+    /* the file-window calls' kernels (val_gpu_plan_file_windows) */
+    VAL_GPU_KERNEL_WINDOWS_COUNT = 14,
+    VAL_GPU_KERNEL_WINDOWS_HASH = 15
 };
 typedef struct val_gpu_launch {
     uint32_t kernel;        /* VAL_GPU_KERNEL_* */
@@ -630,6 +752,24 @@ enum { VAL_GPU_WINDOW_PACK = 0, VAL_GPU_WINDOW_UNPACK = 1, VAL_GPU_WINDOW_UNPACK
  * launches written: 0 for an unknown call or one that launches nothing. */
 uint32_t val_gpu_plan_window(uint32_t call, uint32_t cus, uint32_t n, uint32_t groups,
                              uint32_t max_frames, uint32_t len_hint, val_gpu_launch_t out[4]);
+/* The launches val_crc32_file_windows_dev and the three resume calls would
+ * make for n_files files and windows of at most max_len bytes on a device of
+ * `cus` compute units, in order: the count launch, the prefix sum
+ * (VAL_GPU_KERNEL_SCAN_FIRST) and the hash launch; kernel, grid, count (the
+ * files, or the most chunks the call can have) and, on the count and hash
+ * launches, k0 (log2 of the call's chunk bytes) are set. max_len == 0 is the
+ * count launch alone. Needs no device. Returns the number of launches written:
+ * 0 for n_files == 0 and for a call that is refused (max_len above 2^32, or
+ * the chunk product overflowing 32 bits). */
+uint32_t val_gpu_plan_file_windows(uint32_t cus, uint32_t n_files, uint64_t max_len, val_gpu_launch_t out[3]);
+/* Chunk bytes 2^k0 of the file-window calls: 12..16 force them, 0 restores
+ * the automatic choice (the smallest of 4 .. 64 KiB at which n_files windows
+ * of max_len bytes are at most one chunk per wave of the device); any other
+ * value returns VAL_ERR_INVALID_ARG. A forced value is raised as far as a
+ * call's max_len needs (a window has at most 2^16 chunks) and its chunk
+ * product allows. Speed only; results never change (tests force 12, so that
+ * the multi-chunk paths run on kilobytes). */
+val_status_t val_gpu_set_file_window_chunk(uint32_t k0);
 /* Force the lanes-per-frame geometry (1,2,4,...,64) for later calls of this
  * process; 0 restores the automatic choice. Returns VAL_ERR_INVALID_ARG for
  * other values. Results never depend on it; only speed does. */

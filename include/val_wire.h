@@ -224,6 +224,61 @@ val_status_t val_frame_fill_window(uint64_t next, uint64_t last_acked, uint64_t 
                                    uint8_t *include_offset, uint64_t *frame_off, uint32_t *crc_len,
                                    uint32_t *n_frames, uint64_t *out_used, uint64_t *next_out);
 
+/*
+ * The three rules of a VAL_RESUME_TAIL handshake, host only: which window of a
+ * partial file is hashed, by whom, and what follows from the two CRCs. Each is
+ * stated once; the device calls of val_crc32_gpu.h (val_resume_tail_files_dev,
+ * val_resume_request_files_dev, val_resume_check_files_dev) apply the same
+ * code per file. All arithmetic is 64-bit and never wraps. The NEVER and
+ * SKIP_EXISTING modes hash nothing and are not stated here.
+ *
+ * val_resume_tail_window: the receiver's proposal, the TAIL branch of
+ * determine_resume_action (reference src/val_receiver.c:119-181), for a local
+ * file of `existing` bytes and an incoming file of `incoming` bytes. Returns
+ * the val_resume_action_t value. existing == 0 gives VAL_RESUME_START_ZERO;
+ * existing > incoming gives VAL_RESUME_SKIP_FILE when mismatch_skip is set,
+ * else VAL_RESUME_START_ZERO. Otherwise, with
+ * cap = clamp(tail_cap_bytes ? tail_cap_bytes : 8 MiB, 1, 256 MiB),
+ * verify_len = min(existing, cap), and if min_verify_bytes > 0 and
+ * verify_len < min_verify_bytes then verify_len = min(existing,
+ * min_verify_bytes); the action is VAL_RESUME_VERIFY_FIRST with
+ * *resume_offset = existing, and the window to hash is
+ * [existing - verify_len, existing). For every other action both outputs are
+ * 0. (The reference's remaining START_ZERO exits, a missing receive buffer
+ * and a failed read, are the host's own and not part of the rule.) The
+ * outputs are nullable.
+ */
+#define VAL_RESUME_TAIL_CAP_DEFAULT ((uint64_t)8u << 20)
+#define VAL_RESUME_TAIL_CAP_MAX ((uint64_t)256u << 20)
+int val_resume_tail_window(uint64_t existing, uint64_t incoming, uint64_t tail_cap_bytes, uint64_t min_verify_bytes,
+                           int mismatch_skip, uint64_t *resume_offset, uint64_t *verify_len);
+/*
+ * val_resume_request_window: the sender's clamp of a VERIFY_FIRST answer
+ * (reference src/val_sender.c:208-215): *vlen32 =
+ * (uint32_t)min(verify_len, resume_offset), *start = resume_offset - *vlen32.
+ * The truncation to 32 bits is the reference's (the VERIFY request carries a
+ * 32-bit length) and is kept: a verify_len of 2^32 asks for nothing. Returns 0
+ * when *vlen32 == 0: no VERIFY is sent and the transfer starts at
+ * resume_offset; else 1, and the window to hash in the sender's file is
+ * [*start, *start + *vlen32). The outputs are nullable.
+ */
+int val_resume_request_window(uint64_t resume_offset, uint64_t verify_len, uint64_t *start, uint32_t *vlen32);
+/*
+ * val_resume_verdict: the result the receiver puts into its VERIFY response
+ * and the offset it resumes at (reference src/val_receiver.c:689-721). VAL_OK
+ * iff window_ok && local_crc == sender_crc; otherwise VAL_SKIPPED when
+ * mismatch_skip is set, else VAL_ERR_RESUME_VERIFY. *resume_off_out (nullable)
+ * is rec_resume_off for VAL_OK, file_size (the incoming file's: the file is
+ * skipped) for VAL_SKIPPED and 0 for VAL_ERR_RESUME_VERIFY. window_ok == 0 is
+ * the reference's short read: a requested window that does not lie inside the
+ * local file makes val_internal_crc32_region fail, and the verdict is a
+ * mismatch. This is the rule of :662-722; the reference's earlier site
+ * (:429-456) answers the same request without the skip branch and is not
+ * stated.
+ */
+val_status_t val_resume_verdict(int window_ok, uint32_t local_crc, uint32_t sender_crc, int mismatch_skip,
+                                uint64_t rec_resume_off, uint64_t file_size, uint64_t *resume_off_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,10 @@ EXPORTS = (
     "val_frame_unpack_files_dev",
     "val_frame_scan_work_bytes", "val_frame_scan_streams_dev", "val_gpu_set_scan_front",
     "val_frame_fill_window", "val_frame_fill_work_bytes", "val_frame_fill_files_dev",
+    "val_resume_tail_window", "val_resume_request_window", "val_resume_verdict",
+    "val_file_windows_work_bytes", "val_crc32_file_windows_dev", "val_resume_tail_files_dev",
+    "val_resume_request_files_dev", "val_resume_check_files_dev", "val_gpu_plan_file_windows",
+    "val_gpu_set_file_window_chunk",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -86,6 +90,7 @@ class ValError(RuntimeError):
 KERNEL_RAGGED, KERNEL_SPLIT, KERNEL_FRAMES, KERNEL_FRAMES_C0 = 0, 1, 2, 3
 (KERNEL_PACK, KERNEL_UNPACK_PARSE, KERNEL_UNPACK_ORDER, KERNEL_UNPACK_ORDER_FILES, KERNEL_UNPACK, KERNEL_SCAN_STREAMS,
  KERNEL_SCAN_FIRST, KERNEL_SCAN_COMPACT, KERNEL_FILL_COUNT, KERNEL_FILL_DESC) = range(4, 14)
+KERNEL_WINDOWS_COUNT, KERNEL_WINDOWS_HASH = 14, 15  # val_gpu_plan_file_windows
 # val_gpu_plan_window: the window calls
 WINDOW_PACK, WINDOW_UNPACK, WINDOW_UNPACK_FILES, WINDOW_SCAN, WINDOW_FILL = range(5)
 
@@ -206,6 +211,18 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
     fn("val_gpu_plan_window", u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(Launch))
+    fn("val_resume_tail_window", ctypes.c_int, u64, u64, u64, u64, ctypes.c_int, ctypes.POINTER(u64),
+       ctypes.POINTER(u64))
+    fn("val_resume_request_window", ctypes.c_int, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u32))
+    fn("val_resume_verdict", i32, ctypes.c_int, u32, u32, ctypes.c_int, u64, u64, ctypes.POINTER(u64))
+    fn("val_file_windows_work_bytes", u64, u32)
+    fn("val_crc32_file_windows_dev", i32, _vp, _vp, _vp, _vp, u32, u64, _vp, _vp, _vp, u64, _vp)
+    fn("val_resume_tail_files_dev", i32, _vp, _vp, _vp, u32, u64, u64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, u64, _vp)
+    fn("val_resume_request_files_dev", i32, _vp, _vp, _vp, _vp, _vp, u32, u64, _vp, _vp, _vp, _vp, _vp, u64, _vp)
+    fn("val_resume_check_files_dev", i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, u32, u64, ctypes.c_int, _vp, _vp, _vp,
+       _vp, u64, _vp)
+    fn("val_gpu_plan_file_windows", u32, u32, u32, u64, ctypes.POINTER(Launch))
+    fn("val_gpu_set_file_window_chunk", i32, u32)
 
 
 def lib() -> ctypes.CDLL:
@@ -439,6 +456,21 @@ def plan_window(call: int, cus: int, n: int, *, groups: int = 0, max_frames: int
     out = (Launch * 4)()
     k = lib().val_gpu_plan_window(call, cus, n, groups, max_frames, len_hint, out)
     return [out[i] for i in range(k)]
+
+
+def plan_file_windows(cus: int, n_files: int, max_len: int) -> list:
+    """The launches (Launch, at most three: kernel, grid, count, k0) of
+    wire.file_windows_dev and the resume calls for n_files windows of at most
+    max_len bytes, with the process's current knobs. Needs no GPU."""
+    out = (Launch * 3)()
+    k = lib().val_gpu_plan_file_windows(cus, n_files, max_len, out)
+    return [out[i] for i in range(k)]
+
+
+def set_file_window_chunk(k0: int) -> None:
+    """Force the chunk bytes 2**k0 of the file-window calls: 12..16, 0 =
+    automatic. Speed only."""
+    _check(lib().val_gpu_set_file_window_chunk(k0), "val_gpu_set_file_window_chunk")
 
 
 def set_prefetch(on: int) -> None:

@@ -2,13 +2,15 @@
 // with how many lanes, which round loop and which grid, and whether it takes
 // the dynamic tail, the in-launch tail pieces or the split kernel
 // (plan_frames()); and the lanes and grids of the window calls' launches: the
-// framer, both unpack calls, the scan and the fill (plan_pack(),
-// plan_unpack(), plan_scan(), plan_fill()). They map plain numbers to
+// framer, both unpack calls, the scan, the fill and the file windows
+// (plan_pack(), plan_unpack(), plan_scan(), plan_fill(),
+// plan_file_windows()). They map plain numbers to
 // launches and call no HIP API; val_crc32_hip.hip fills in the kernels'
 // params, executes a plan and decides nothing. tests/test_launch_plan.py pins
 // the plans of a table of shapes through val_gpu_plan_frames() and
-// val_gpu_plan_window(). Every threshold here is a measured result; the
-// experiments are in DESIGN_EXPERIMENTS.md.
+// val_gpu_plan_window(), tests/test_launch_plan_windows.py those of
+// val_gpu_plan_file_windows(). Every threshold here is a measured result; the
+// experiments are in DESIGN_EXPERIMENTS.md and DESIGN.md section 5.
 #pragma once
 #include <stdint.h>
 
@@ -20,6 +22,7 @@
 #include "scan_kernel.hpp"
 #include "unpack_kernel.hpp"
 #include "val_crc32_gpu.h"
+#include "windows_kernel.hpp"
 
 namespace vcrc {
 
@@ -81,6 +84,7 @@ struct PlanKnobs {
     bool dyn_tail, split, tail_pieces;
     uint32_t ragged_min;
     uint32_t scan_front;  // 0 = by the number of streams
+    uint32_t window_k0;   // file windows: log2 of the chunk bytes, 0 = automatic
 };
 
 using Launch = val_gpu_launch_t;
@@ -431,6 +435,53 @@ inline WindowPlan plan_fill(uint32_t cus, uint32_t n_files, uint32_t max_frames,
     const uint64_t cap = (uint64_t)std::max(cus, 1u) * kFillBlocksPerCU;
     pl.add(VAL_GPU_KERNEL_FILL_DESC, std::min<uint64_t>((slots + kFillBlock - 1) / kFillBlock, cap), slots);
     return plan_pack(cus, (uint32_t)slots, (uint32_t)(mtu - VAL_WIRE_TRAILER_SIZE), k, pl);
+}
+
+// File windows (windows_kernel.hpp): the count launch of one thread per file,
+// the prefix sum, then the hash in a persistent grid of at most one workgroup
+// per CU (the kernel holds the LDS tables), sized for the most chunks the call
+// can have, n_files * ceil(max_len / W): the host does not know the lengths.
+// W = 2^k0 is one chunk size for the whole call. Automatic: the smallest of
+// 4 .. 64 KiB at which that bound is at most one chunk per wave of the machine
+// (region_geometry's idea: a single 8 MiB window gets 4 KiB chunks, 256 MiB get
+// 64 KiB), and 64 KiB when none is. Against every forced k0 on four batch
+// shapes it was the fastest or within 1% of it (profiles/resume_timing.json,
+// DESIGN.md section 5); other shapes have not been timed. A forced
+// k0 (val_gpu_set_file_window_chunk) is taken, and like the automatic one
+// raised as far as the fold needs: at most 2^16 chunks per window (16 maps) and
+// fewer than 2^32 chunks in all. A call that needs more than 64 KiB for either
+// (max_len above 2^32, or the bound overflowing 32 bits at 64 KiB) is refused
+// and has no plan. max_len == 0 hashes nothing: the count launch alone
+// finishes every file.
+inline uint64_t window_chunks(uint32_t n_files, uint64_t max_len, uint32_t k0)
+{
+    return (uint64_t)n_files * ((max_len >> k0) + ((max_len & (((uint64_t)1 << k0) - 1u)) ? 1u : 0u));
+}
+
+inline bool file_windows_fit(uint32_t n_files, uint64_t max_len)
+{
+    return max_len <= kWinMaxLen && window_chunks(n_files, max_len, kWinK0Max) <= UINT32_MAX;
+}
+
+inline WindowPlan plan_file_windows(uint32_t cus32, uint32_t n_files, uint64_t max_len, const PlanKnobs &k)
+{
+    WindowPlan pl;
+    if (n_files == 0 || !file_windows_fit(n_files, max_len)) return pl;
+    const uint64_t cus = (uint64_t)std::max(cus32, 1u);
+    uint32_t k0 = k.window_k0 ? k.window_k0 : kWinK0Min;
+    if (!k.window_k0)
+        while (k0 < kWinK0Max && window_chunks(n_files, max_len, k0) > cus * kWavesPerBlock) k0++;
+    while (k0 < kWinK0Max &&
+           (max_len > ((uint64_t)1 << (k0 + kNumPowMaps)) || window_chunks(n_files, max_len, k0) > UINT32_MAX))
+        k0++;
+    pl.add(VAL_GPU_KERNEL_WINDOWS_COUNT, ((uint64_t)n_files + kWinCountBlock - 1) / kWinCountBlock, n_files);
+    pl.launch[0].k0 = k0;
+    if (max_len == 0) return pl;
+    pl.add(VAL_GPU_KERNEL_SCAN_FIRST, 1, n_files);
+    const uint64_t chunks = window_chunks(n_files, max_len, k0);
+    pl.add(VAL_GPU_KERNEL_WINDOWS_HASH, std::min<uint64_t>((chunks + kWavesPerBlock - 1) / kWavesPerBlock, cus), chunks);
+    pl.launch[2].k0 = k0;
+    return pl;
 }
 
 }  // namespace vcrc

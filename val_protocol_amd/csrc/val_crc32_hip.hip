@@ -334,6 +334,7 @@ val_status_t launch_at_lanes(uint32_t lanes, const char *what, F &&launch)
 std::atomic<uint32_t> g_forced_lanes{0};
 std::atomic<int> g_forced_prefetch{-1};
 std::atomic<uint32_t> g_scan_front{0};  // val_gpu_set_scan_front: 0 = by the number of streams
+std::atomic<uint32_t> g_window_k0{0};   // val_gpu_set_file_window_chunk: 0 = automatic
 
 uint32_t env_u32(const char *name)
 {
@@ -661,7 +662,8 @@ uint32_t ragged_min_frames()
 PlanKnobs plan_knobs()
 {
     return PlanKnobs{forced_lanes(), forced_prefetch(), dyn_tail_enabled(), split_enabled(), tail_pieces_enabled(),
-                     ragged_min_frames(), g_scan_front.load(std::memory_order_relaxed)};
+                     ragged_min_frames(), g_scan_front.load(std::memory_order_relaxed),
+                     g_window_k0.load(std::memory_order_relaxed)};
 }
 
 // Frames [l.first, l.first + l.count) of batch p as a batch of their own, with
@@ -1834,6 +1836,65 @@ uint64_t fill_work(uint32_t n_files, uint32_t max_frames, void *d_work, FillPara
     return (w.used + 7u) & ~(uint64_t)7;
 }
 
+// Workspace of the file-window calls: per file the window's absolute address
+// and length (u64), its chunk count, accumulator and arrival count (u32), and
+// the n_files + 1 entries of the chunks' prefix sum (u32).
+uint64_t windows_work(uint32_t n_files, void *d_work, WinParams &p)
+{
+    Carve w{(uintptr_t)d_work};
+    p.wbase = w.take<uint64_t>(n_files);
+    p.wlen = w.take<uint64_t>(n_files);
+    p.first = w.take<uint32_t>((uint64_t)n_files + 1u);
+    p.wcnt = w.take<uint32_t>(n_files);
+    p.acc = w.take<uint32_t>(n_files);
+    p.arrived = w.take<uint32_t>(n_files);
+    return (w.used + 7u) & ~(uint64_t)7;
+}
+
+// The checks the four file-window calls share, in the order the header gives;
+// they place the workspace in p.
+val_status_t windows_checks(uint32_t n_files, uint64_t max_len, void *d_work, uint64_t work_bytes, WinParams &p)
+{
+    val_status_t st = check_work(d_work, work_bytes, windows_work(n_files, d_work, p),
+                                 "work_bytes below val_file_windows_work_bytes(n_files)");
+    if (st != VAL_OK) return st;
+    if (max_len > kWinMaxLen) return fail(VAL_ERR_INVALID_ARG, "max_len above 2^32");
+    if (!file_windows_fit(n_files, max_len))
+        return fail(VAL_ERR_INVALID_ARG, "n_files * chunks per file overflows 32 bits");
+    return VAL_OK;
+}
+
+// The pipeline of the file-window calls: p holds the mode, its inputs and
+// outputs and the workspace (windows_checks).
+val_status_t windows_launch(WinParams &p, uint32_t n_files, uint64_t max_len, void *stream)
+{
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    val_status_t st = cur_dev(stream, p.wbase, &c);
+    if (st != VAL_OK) return st;
+    const hipStream_t s = pick_stream(stream);
+    const WindowPlan plan = plan_file_windows((uint32_t)c->cus, n_files, max_len, plan_knobs());
+    p.n_files = n_files;
+    p.max_len = max_len;
+    p.k0 = plan.launch[0].k0;
+    p.consts = c->d_consts;
+    // 1. the rule, the window's validation, its chunk count; files without chunks are finished
+    hipLaunchKernelGGL(k_win_count, dim3(plan.launch[0].grid), dim3(kWinCountBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_win_count launch");
+    if (plan.count < 3) return VAL_OK;  // max_len == 0: nothing to hash
+    // 2. first: the scan call's kernel over the chunk counts
+    ScanParams sp{};
+    sp.n_streams = n_files;
+    sp.wcnt = p.wcnt;
+    sp.first = p.first;
+    hipLaunchKernelGGL(k_scan_first, dim3(plan.launch[1].grid), dim3(kScanFirstBlock), 0, s, sp);
+    VCRC_HIP(hipGetLastError(), "k_scan_first launch");
+    // 3. the chunks of all files; the last to arrive finishes its file
+    hipLaunchKernelGGL(k_win_hash, dim3(plan.launch[2].grid), dim3(kBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_win_hash launch");
+    return VAL_OK;
+}
+
 }  // namespace vcrc
 
 using namespace vcrc;
@@ -2478,6 +2539,155 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
     p.out_hdr = d_hdr;
     p.consts = c->d_consts;
     return pack_launch(p, pack, s);
+}
+
+uint64_t val_file_windows_work_bytes(uint32_t n_files)
+{
+    WinParams p{};
+    return windows_work(n_files, nullptr, p);
+}
+
+val_status_t val_gpu_set_file_window_chunk(uint32_t k0)
+{
+    if (k0 != 0 && (k0 < kWinK0Min || k0 > kWinK0Max))
+        return fail(VAL_ERR_INVALID_ARG, "file window chunk must be 0 or 12..16 (log2 of its bytes)");
+    g_window_k0.store(k0, std::memory_order_relaxed);
+    return VAL_OK;
+}
+
+uint32_t val_gpu_plan_file_windows(uint32_t cus, uint32_t n_files, uint64_t max_len, val_gpu_launch_t out[3])
+{
+    const WindowPlan plan = plan_file_windows(cus, n_files, max_len, plan_knobs());
+    for (uint32_t i = 0; out && i < plan.count; i++) out[i] = plan.launch[i];
+    return plan.count;
+}
+
+val_status_t val_crc32_file_windows_dev(const uint64_t *d_file_ptr, const uint64_t *d_file_size,
+                                        const uint64_t *d_win_off, const uint64_t *d_win_len, uint32_t n_files,
+                                        uint64_t max_len, uint32_t *d_crc, int32_t *d_status, void *d_work,
+                                        uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    WinParams p{};
+    val_status_t st = windows_checks(n_files, max_len, d_work, work_bytes, p);
+    if (st != VAL_OK) return st;
+    if (n_files == 0) return VAL_OK;
+    if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
+    if (!d_file_size) return fail(VAL_ERR_INVALID_ARG, "file_size is NULL");
+    if (!d_win_off) return fail(VAL_ERR_INVALID_ARG, "win_off is NULL");
+    if (!d_win_len) return fail(VAL_ERR_INVALID_ARG, "win_len is NULL");
+    if (!d_crc) return fail(VAL_ERR_INVALID_ARG, "crc is NULL");
+    p.mode = kWinGeneric;
+    p.file_ptr = d_file_ptr;
+    p.file_size = d_file_size;
+    p.win_off = d_win_off;
+    p.win_len = d_win_len;
+    p.out_crc = d_crc;
+    p.out_status = d_status;
+    return windows_launch(p, n_files, max_len, stream);
+}
+
+val_status_t val_resume_tail_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_existing,
+                                       const uint64_t *d_incoming, uint32_t n_files, uint64_t tail_cap_bytes,
+                                       uint64_t min_verify_bytes, int mismatch_skip, int32_t *d_action,
+                                       uint64_t *d_resume_off, uint64_t *d_verify_len, uint32_t *d_verify_crc,
+                                       void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    if (min_verify_bytes > kWinMaxLen) return fail(VAL_ERR_INVALID_ARG, "min_verify_bytes above 2^32");
+    const uint64_t max_len = val_rule_tail_max_len(tail_cap_bytes, min_verify_bytes);
+    WinParams p{};
+    val_status_t st = windows_checks(n_files, max_len, d_work, work_bytes, p);
+    if (st != VAL_OK) return st;
+    if (n_files == 0) return VAL_OK;
+    if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
+    if (!d_existing) return fail(VAL_ERR_INVALID_ARG, "existing is NULL");
+    if (!d_incoming) return fail(VAL_ERR_INVALID_ARG, "incoming is NULL");
+    if (!d_action) return fail(VAL_ERR_INVALID_ARG, "action is NULL");
+    if (!d_resume_off) return fail(VAL_ERR_INVALID_ARG, "resume_off is NULL");
+    if (!d_verify_len) return fail(VAL_ERR_INVALID_ARG, "verify_len is NULL");
+    if (!d_verify_crc) return fail(VAL_ERR_INVALID_ARG, "verify_crc is NULL");
+    p.mode = kWinTail;
+    p.file_ptr = d_file_ptr;
+    p.file_size = d_existing;
+    p.incoming = d_incoming;
+    p.tail_cap = tail_cap_bytes;
+    p.min_verify = min_verify_bytes;
+    p.mismatch_skip = mismatch_skip != 0;
+    p.out_action = d_action;
+    p.out_off = d_resume_off;
+    p.out_len64 = d_verify_len;
+    p.out_crc = d_verify_crc;
+    return windows_launch(p, n_files, max_len, stream);
+}
+
+val_status_t val_resume_request_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_file_size,
+                                          const int32_t *d_action, const uint64_t *d_resume_off,
+                                          const uint64_t *d_verify_len, uint32_t n_files, uint64_t max_len,
+                                          uint64_t *d_req_off, uint32_t *d_req_len, uint32_t *d_req_crc,
+                                          int32_t *d_status, void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    WinParams p{};
+    val_status_t st = windows_checks(n_files, max_len, d_work, work_bytes, p);
+    if (st != VAL_OK) return st;
+    if (n_files == 0) return VAL_OK;
+    if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
+    if (!d_file_size) return fail(VAL_ERR_INVALID_ARG, "file_size is NULL");
+    if (!d_action) return fail(VAL_ERR_INVALID_ARG, "action is NULL");
+    if (!d_resume_off) return fail(VAL_ERR_INVALID_ARG, "resume_off is NULL");
+    if (!d_verify_len) return fail(VAL_ERR_INVALID_ARG, "verify_len is NULL");
+    if (!d_req_off) return fail(VAL_ERR_INVALID_ARG, "req_off is NULL");
+    if (!d_req_len) return fail(VAL_ERR_INVALID_ARG, "req_len is NULL");
+    if (!d_req_crc) return fail(VAL_ERR_INVALID_ARG, "req_crc is NULL");
+    p.mode = kWinRequest;
+    p.file_ptr = d_file_ptr;
+    p.file_size = d_file_size;
+    p.action = d_action;
+    p.resume_off = d_resume_off;
+    p.verify_len = d_verify_len;
+    p.out_off = d_req_off;
+    p.out_len32 = d_req_len;
+    p.out_crc = d_req_crc;
+    p.out_status = d_status;
+    return windows_launch(p, n_files, max_len, stream);
+}
+
+val_status_t val_resume_check_files_dev(const uint64_t *d_file_ptr, const uint64_t *d_existing,
+                                        const uint64_t *d_incoming, const int32_t *d_action,
+                                        const uint64_t *d_req_off, const uint32_t *d_req_len,
+                                        const uint32_t *d_req_crc, const uint64_t *d_rec_resume_off, uint32_t n_files,
+                                        uint64_t max_len, int mismatch_skip, uint32_t *d_local_crc, int32_t *d_result,
+                                        uint64_t *d_written, void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    WinParams p{};
+    val_status_t st = windows_checks(n_files, max_len, d_work, work_bytes, p);
+    if (st != VAL_OK) return st;
+    if (n_files == 0) return VAL_OK;
+    if (!d_file_ptr) return fail(VAL_ERR_INVALID_ARG, "file_ptr is NULL");
+    if (!d_existing) return fail(VAL_ERR_INVALID_ARG, "existing is NULL");
+    if (!d_incoming) return fail(VAL_ERR_INVALID_ARG, "incoming is NULL");
+    if (!d_req_off) return fail(VAL_ERR_INVALID_ARG, "req_off is NULL");
+    if (!d_req_len) return fail(VAL_ERR_INVALID_ARG, "req_len is NULL");
+    if (!d_req_crc) return fail(VAL_ERR_INVALID_ARG, "req_crc is NULL");
+    if (!d_rec_resume_off) return fail(VAL_ERR_INVALID_ARG, "rec_resume_off is NULL");
+    if (!d_result) return fail(VAL_ERR_INVALID_ARG, "result is NULL");
+    if (!d_written) return fail(VAL_ERR_INVALID_ARG, "written is NULL");
+    p.mode = kWinCheck;
+    p.file_ptr = d_file_ptr;
+    p.file_size = d_existing;
+    p.incoming = d_incoming;
+    p.action = d_action;
+    p.win_off = d_req_off;
+    p.req_len = d_req_len;
+    p.req_crc = d_req_crc;
+    p.resume_off = d_rec_resume_off;
+    p.mismatch_skip = mismatch_skip != 0;
+    p.out_crc = d_local_crc;
+    p.out_status = d_result;
+    p.out_off = d_written;
+    return windows_launch(p, n_files, max_len, stream);
 }
 
 val_status_t val_crc32_region_dev(const uint8_t *d_ptr, uint64_t len, uint32_t state_in, uint32_t *d_state_out,

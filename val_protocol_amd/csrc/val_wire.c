@@ -15,6 +15,8 @@
 #include "val_byte_order.h"
 #include "val_wire.h"
 
+#include "resume_rules.h"
+
 void val_serialize_frame_header(uint8_t type, uint8_t flags, uint16_t content_len, uint32_t type_data, uint8_t *wiredata)
 {
     if (!wiredata)
@@ -405,5 +407,40 @@ val_status_t val_frame_fill_window(uint64_t next, uint64_t last_acked, uint64_t 
         *out_used = used;
     if (next_out)
         *next_out = next;
+    return st;
+}
+
+/* The resume rules: bodies in resume_rules.h, which the device code shares. */
+int val_resume_tail_window(uint64_t existing, uint64_t incoming, uint64_t tail_cap_bytes, uint64_t min_verify_bytes,
+                           int mismatch_skip, uint64_t *resume_offset, uint64_t *verify_len)
+{
+    uint64_t off = 0, len = 0;
+    const int action = val_rule_tail_window(existing, incoming, tail_cap_bytes, min_verify_bytes, mismatch_skip, &off, &len);
+    if (resume_offset)
+        *resume_offset = off;
+    if (verify_len)
+        *verify_len = len;
+    return action;
+}
+
+int val_resume_request_window(uint64_t resume_offset, uint64_t verify_len, uint64_t *start, uint32_t *vlen32)
+{
+    uint64_t s = 0;
+    uint32_t v = 0;
+    const int send = val_rule_request_window(resume_offset, verify_len, &s, &v);
+    if (start)
+        *start = s;
+    if (vlen32)
+        *vlen32 = v;
+    return send;
+}
+
+val_status_t val_resume_verdict(int window_ok, uint32_t local_crc, uint32_t sender_crc, int mismatch_skip,
+                                uint64_t rec_resume_off, uint64_t file_size, uint64_t *resume_off_out)
+{
+    uint64_t off = 0;
+    const val_status_t st = val_rule_verdict(window_ok, local_crc, sender_crc, mismatch_skip, rec_resume_off, file_size, &off);
+    if (resume_off_out)
+        *resume_off_out = off;
     return st;
 }

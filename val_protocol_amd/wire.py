@@ -412,6 +412,170 @@ def fill_files_dev(payload, file_pos, file_size, next, last_acked, mtu: int, max
     return frame_off, crc_len, crc, first, nframes, stream_len
 
 
+def resume_tail_window(existing: int, incoming: int, tail_cap_bytes: int = 0, min_verify_bytes: int = 0,
+                       mismatch_skip: bool = False):
+    """The receiver's resume proposal under VAL_RESUME_TAIL
+    (val_resume_tail_window; host only). Returns (action, resume_offset,
+    verify_len): for VAL_RESUME_VERIFY_FIRST (2) the window to hash is
+    [existing - verify_len, existing); for every other action both are 0."""
+    off, vlen = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    action = lib().val_resume_tail_window(existing, incoming, tail_cap_bytes, min_verify_bytes, int(mismatch_skip),
+                                          ctypes.byref(off), ctypes.byref(vlen))
+    return int(action), int(off.value), int(vlen.value)
+
+
+def resume_request_window(resume_offset: int, verify_len: int):
+    """The sender's clamp of a VERIFY_FIRST answer (val_resume_request_window;
+    host only). Returns (send, start, vlen32): send is False when the window is
+    empty (no VERIFY goes out; the transfer starts at resume_offset)."""
+    start, v32 = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    send = lib().val_resume_request_window(resume_offset, verify_len, ctypes.byref(start), ctypes.byref(v32))
+    return bool(send), int(start.value), int(v32.value)
+
+
+def resume_verdict(window_ok: bool, local_crc: int, sender_crc: int, mismatch_skip: bool, rec_resume_off: int,
+                   file_size: int):
+    """The receiver's VERIFY result and the offset it resumes at
+    (val_resume_verdict; host only). Returns (status, resume_offset)."""
+    off = ctypes.c_uint64(0)
+    st = lib().val_resume_verdict(int(bool(window_ok)), local_crc & 0xFFFFFFFF, sender_crc & 0xFFFFFFFF,
+                                  int(mismatch_skip), rec_resume_off, file_size, ctypes.byref(off))
+    return int(st), int(off.value)
+
+
+def file_windows_work_bytes(n_files: int) -> int:
+    """Workspace bytes file_windows_dev and the resume calls need."""
+    return int(lib().val_file_windows_work_bytes(n_files))
+
+
+def _windows_call(fresh, work, stream, dev, n_files):
+    """The workspace and the stream ordering the file-window wrappers share."""
+    import torch
+
+    if work is None:
+        work = torch.empty(max(file_windows_work_bytes(n_files), 16), dtype=torch.uint8, device=dev)
+        fresh = fresh + [work]
+    if stream is not None:  # the allocations are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    return work
+
+
+def _per_file(n, **tensors):
+    for name, t in tensors.items():
+        if t is not None and int(t.numel()) != n:
+            raise ValueError(f"{name} needs one entry per file")
+
+
+def file_windows_dev(file_ptr, file_size, win_off, win_len, max_len: int, *, want_status: bool = True, work=None,
+                     stream=None):
+    """CRC-32 of one window per GPU-resident file (val_crc32_file_windows_dev):
+    three launches on torch's current stream (or ``stream``), returns at once.
+
+    ``file_ptr`` (device addresses), ``file_size``, ``win_off`` and ``win_len``
+    are int64[S] tensors on the GPU holding uint64 bit patterns. Returns
+    (crc int32[S], status int32[S] or None): the finalized CRC of
+    ``[win_off, win_off + win_len)`` of each file; a window outside its file
+    or longer than ``max_len`` gets status VAL_ERR_INVALID_ARG and crc 0, and
+    none of its bytes is read."""
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    S = int(file_ptr.numel())
+    _per_file(S, file_size=file_size, win_off=win_off, win_len=win_len)
+    dev = file_ptr.device
+    crc = torch.empty(S, dtype=torch.int32, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev) if want_status else None
+    work = _windows_call([crc] + ([status] if want_status else []), work, stream, dev, S)
+    st = lib().val_crc32_file_windows_dev(_dptr(file_ptr), _dptr(file_size), _dptr(win_off), _dptr(win_len), S, max_len,
+                                          _dptr(crc), _dptr(status), _dptr(work), int(work.numel()),
+                                          _stream_ptr(stream))
+    _check(st, "val_crc32_file_windows_dev")
+    return crc, status
+
+
+def resume_tail_files_dev(file_ptr, existing, incoming, *, tail_cap_bytes: int = 0, min_verify_bytes: int = 0,
+                          mismatch_skip: bool = False, work=None, stream=None):
+    """The receiver's resume proposal for S GPU-resident files
+    (val_resume_tail_files_dev): resume_tail_window per file, and the tail
+    window's CRC for VERIFY_FIRST files. ``existing`` (int64[S]) can be the
+    ``written`` of unpack_data_files_dev on the same stream. Returns (action
+    int32[S], resume_off int64[S], verify_len int64[S], verify_crc int32[S])."""
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    S = int(file_ptr.numel())
+    _per_file(S, existing=existing, incoming=incoming)
+    dev = file_ptr.device
+    action = torch.empty(S, dtype=torch.int32, device=dev)
+    resume_off = torch.empty(S, dtype=torch.int64, device=dev)
+    verify_len = torch.empty(S, dtype=torch.int64, device=dev)
+    verify_crc = torch.empty(S, dtype=torch.int32, device=dev)
+    work = _windows_call([action, resume_off, verify_len, verify_crc], work, stream, dev, S)
+    st = lib().val_resume_tail_files_dev(_dptr(file_ptr), _dptr(existing), _dptr(incoming), S, tail_cap_bytes,
+                                         min_verify_bytes, int(mismatch_skip), _dptr(action), _dptr(resume_off),
+                                         _dptr(verify_len), _dptr(verify_crc), _dptr(work), int(work.numel()),
+                                         _stream_ptr(stream))
+    _check(st, "val_resume_tail_files_dev")
+    return action, resume_off, verify_len, verify_crc
+
+
+def resume_request_files_dev(file_ptr, file_size, action, resume_off, verify_len, max_len: int, *,
+                             want_status: bool = True, work=None, stream=None):
+    """The sender's answer for S GPU-resident files
+    (val_resume_request_files_dev): resume_request_window per VERIFY_FIRST
+    file and the CRC of that window of the sender's file. Returns (req_off
+    int64[S], req_len int32[S], req_crc int32[S], status int32[S] or None);
+    files with another action or an empty window get (resume_off, 0, 0,
+    VAL_OK)."""
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    S = int(file_ptr.numel())
+    _per_file(S, file_size=file_size, action=action, resume_off=resume_off, verify_len=verify_len)
+    dev = file_ptr.device
+    req_off = torch.empty(S, dtype=torch.int64, device=dev)
+    req_len = torch.empty(S, dtype=torch.int32, device=dev)
+    req_crc = torch.empty(S, dtype=torch.int32, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev) if want_status else None
+    work = _windows_call([req_off, req_len, req_crc] + ([status] if want_status else []), work, stream, dev, S)
+    st = lib().val_resume_request_files_dev(_dptr(file_ptr), _dptr(file_size), _dptr(action), _dptr(resume_off),
+                                            _dptr(verify_len), S, max_len, _dptr(req_off), _dptr(req_len),
+                                            _dptr(req_crc), _dptr(status), _dptr(work), int(work.numel()),
+                                            _stream_ptr(stream))
+    _check(st, "val_resume_request_files_dev")
+    return req_off, req_len, req_crc, status
+
+
+def resume_check_files_dev(file_ptr, existing, incoming, req_off, req_len, req_crc, rec_resume_off, max_len: int, *,
+                           result, written, action=None, local_crc=None, mismatch_skip: bool = False, work=None,
+                           stream=None):
+    """The receiver's check of the VERIFY requests of S GPU-resident files
+    (val_resume_check_files_dev): the CRC of the requested window of the local
+    file and resume_verdict. For VERIFY_FIRST files (``action`` None: all)
+    ``result`` (int32[S]), ``written`` (int64[S]: the offset the transfer
+    resumes at) and ``local_crc`` (int32[S], optional) are written in place;
+    the entries of every other file keep their values. ``written`` then feeds
+    unpack_data_files_dev, and ``next`` / ``last_acked`` of fill_files_dev on
+    the peer."""
+    from .crc import _dptr, _stream_ptr
+
+    S = int(file_ptr.numel())
+    _per_file(S, existing=existing, incoming=incoming, req_off=req_off, req_len=req_len, req_crc=req_crc,
+              rec_resume_off=rec_resume_off, result=result, written=written, action=action, local_crc=local_crc)
+    work = _windows_call([], work, stream, file_ptr.device, S)
+    st = lib().val_resume_check_files_dev(_dptr(file_ptr), _dptr(existing), _dptr(incoming), _dptr(action),
+                                          _dptr(req_off), _dptr(req_len), _dptr(req_crc), _dptr(rec_resume_off), S,
+                                          max_len, int(mismatch_skip), _dptr(local_crc), _dptr(result), _dptr(written),
+                                          _dptr(work), int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_resume_check_files_dev")
+    return result, written, local_crc
+
+
 def payload_lens(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     """Payload bytes of each frame (val_frame_payload_lens)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -443,4 +607,6 @@ def data_offsets(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
 __all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_data_batch_dev", "data_layout",
            "unpack_data_batch_dev", "unpack_data_files_dev", "unpack_work_bytes", "frame_accept", "NOT_ACCEPTED", "put_trailers", "scan_frames", "scan_streams_dev", "scan_work_bytes", "payload_lens",
            "fill_window", "fill_files_dev", "fill_work_bytes",
+           "resume_tail_window", "resume_request_window", "resume_verdict", "file_windows_dev",
+           "resume_tail_files_dev", "resume_request_files_dev", "resume_check_files_dev", "file_windows_work_bytes",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

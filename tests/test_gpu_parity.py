@@ -542,24 +542,38 @@ def test_wave_round_tail(vc, dev, L, extra):
 
 
 @pytest.mark.parametrize("strided,payload,per", [
-    (True, 16384, 8),    # strided groups of 8 x 16 KiB: one queue word
-    (False, 65516, 4),   # descriptor groups of 4 x 64 KiB: one queue word
-    (True, 4184, 8),     # strided groups of 8 x 4.2 KiB (34 KB): 64 queue partitions
-    (False, 4184, 8),    # descriptor groups of 8 x 4.2 KiB: 64 queue partitions
-    (False, 1084, 16),   # descriptor groups of 16 x 1.1 KiB: 64 queue partitions, dequeued one group ahead
+    (True, 16384, 8),    # strided groups of 8 x 16 KiB: static (one queue word from 12 rounds)
+    (False, 65516, 4),   # descriptor groups of 4 x 64 KiB: static (one queue word from 6 rounds)
+    (True, 4184, 8),     # strided groups of 8 x 4.2 KiB (34 KB): static (64 partitions from 46 rounds)
+    (False, 4184, 8),    # descriptor groups of 8 x 4.2 KiB: static (the same rule)
+    (False, 1084, 16),   # descriptor groups of 16 x 1.1 KiB, 8 rounds: 64 queue partitions, dequeued one group ahead
 ])
 def test_dynamic_tail_every_frame(vc, dev, strided, payload, per):
-    """Launches long enough for the dynamic tail (k_frames: the last half of
-    the group rounds come from a queue, one word for long groups, 64
-    partitions for shorter ones): 4 full rounds of the machine plus a partial
-    one, every frame checked against the oracle, then the same batch again
-    (the queue must have been re-zeroed by the previous launch)."""
+    """Multi-pass launches with a partial last round, every frame checked
+    against the oracle, then the same batch again. At 4 lanes per frame (the
+    last parameter) 8 full rounds are long enough for the dynamic tail
+    (k_frames: the last half of the group rounds come from the 64 partitions
+    of the queue, which the previous launch must have re-zeroed). At 8 and 16
+    lanes the queue needs 1.45 MiB of frames per wave (launch_plan.hpp
+    kDynMinWaveBytes: 6 GB and more), so these 4-round batches are static
+    multi-pass launches with the frames of the partial round hashed in pieces
+    or in a second launch; tests/test_gpu_dyn_queue.py and the 8 GiB shapes
+    reach the queues at those lanes. Which of the two a parameter gets is
+    asserted from the plan."""
     vc.set_geometry()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    n = cus * 16 * per * 4 + 777
+    rounds, qparts = (8, 64) if per == 16 else (4, 0)
+    n = cus * 16 * per * rounds + 777
     flen = 8 + 8 + payload
     stride = flen + 4
     assert vc.lanes_per_frame(flen) == 64 // per
+    plan = vc.plan_frames(cus, n, flen, descriptors=not strided, flen=flen if strided else 0)
+    assert plan[0].kernel == vc.KERNEL_FRAMES and plan[0].lanes == 64 // per, plan[0].astuple()
+    assert plan[0].qparts == qparts, plan[0].astuple()
+    assert plan[0].count == cus * 16 * per * rounds and plan[0].count + plan[0].tail_n + sum(l.count for l in plan[1:]) == n
+    if qparts:
+        assert plan[0].static_rounds >= 1
+        assert plan[0].count - plan[0].static_rounds * cus * 16 * per >= cus * 16 * per
     g = torch.Generator(device=dev).manual_seed(11)
     buf = torch.randint(0, 256, (n * stride,), dtype=torch.uint8, device=dev, generator=g)
     kw = dict(stride=stride, flen=flen, n=n) if strided else dict(
@@ -569,7 +583,8 @@ def test_dynamic_tail_every_frame(vc, dev, strided, payload, per):
     offs = np.arange(n, dtype=np.uint64) * np.uint64(stride)
     want = _oracle.frames(host, offs, np.full(n, flen, np.uint32), nthreads=16)
     for _ in range(2):
-        crc = vc.frames(buf, **kw)
+        # a fresh output each time: a group the second launch skipped must not find the first one's value
+        crc = vc.frames(buf, out_crc=torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device=dev), **kw)
         torch.cuda.synchronize()
         assert np.array_equal(_u32(crc), want)
 

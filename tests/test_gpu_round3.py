@@ -113,22 +113,35 @@ def test_short_verify_detects_corruption(vc, dev):
 
 
 def test_short_dynamic_tail_every_frame(vc, dev):
-    # long enough for the partitioned dynamic-tail queue (>= 4 group rounds of
-    # 16 KiB+ descriptor groups): 300,000 x 1,100 B, strided and descriptor,
-    # twice on one stream (the last wave out re-zeroes the queue)
+    # long enough for the partitioned dynamic-tail queue: 4 lanes per frame
+    # take it from 8 group rounds (launch_plan.hpp kDynMinRoundsShort) of
+    # 16 KiB+ descriptor groups. 8 rounds and 300 frames of 1,100 B, strided
+    # and descriptor, twice on one stream (the last workgroup out re-zeroes
+    # the queue). The strided call stays static at any length: its groups of
+    # 16 x 1,100 B = 17.6 KiB are under the 32 KiB that strided batches need
+    # for the partitions. Both are asserted from the plan.
     vc.set_geometry()
-    n, L = 300000, 1100
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    L = 1100
+    n = cus * 16 * 16 * 8 + 300
     stride = L + 4
-    base = _prng.prng_bytes(4001, n * stride + 8)
-    d = torch.from_numpy(base).to(dev)
-    want = _oracle.frames_strided(base, stride, L, n, nthreads=8)
+    plan = vc.plan_frames(cus, n, L, descriptors=True)
+    assert (plan[0].kernel, plan[0].lanes, plan[0].qparts) == (vc.KERNEL_FRAMES, 4, 64), plan[0].astuple()
+    assert plan[0].static_rounds >= 1
+    assert plan[0].count - plan[0].static_rounds * cus * 16 * 16 >= cus * 16 * 16
+    plan_s = vc.plan_frames(cus, n, L, flen=L)
+    assert (plan_s[0].kernel, plan_s[0].lanes, plan_s[0].qparts) == (vc.KERNEL_FRAMES, 4, 0), plan_s[0].astuple()
+    g = torch.Generator(device=dev).manual_seed(4001)
+    d = torch.randint(0, 256, (n * stride + 8,), dtype=torch.uint8, device=dev, generator=g)
+    want = _oracle.frames_strided(d.cpu().numpy(), stride, L, n, nthreads=16)
     offs = torch.arange(n, dtype=torch.int64, device=dev) * stride
     lens = torch.full((n,), L, dtype=torch.int32, device=dev)
     for _ in range(2):
-        crc = vc.frames(d, stride=stride, flen=L, n=n)
+        crc = vc.frames(d, stride=stride, flen=L, n=n, out_crc=torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device=dev))
         torch.cuda.synchronize()
         assert np.array_equal(_u32(crc), want)
-        crc = vc.frames(d, off=offs, length=lens, len_hint=L)
+        crc = vc.frames(d, off=offs, length=lens, len_hint=L,
+                        out_crc=torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device=dev))
         torch.cuda.synchronize()
         assert np.array_equal(_u32(crc), want)
 

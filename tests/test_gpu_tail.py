@@ -67,7 +67,7 @@ def _run_both(vc, fn):
     (65532, 2, 41),
     (16400, 1, 100),    # 8 lanes, 17 pieces of 1 KiB per frame (the front one 16 B)
     (8192, 1, 3),       # the shortest frames that take the path: 8 pieces
-    (24580, 4, 777),    # with the dynamic tail (four rounds)
+    (24580, 4, 777),    # four static rounds in front of the pieces (8 lanes take the dynamic tail from 1.45 MiB per wave)
 ])
 def test_strided_tail_every_frame(vc, flen, rounds, tail):
     G = vc.lanes_per_frame(flen)
@@ -106,9 +106,18 @@ def test_descriptor_tail_short_and_empty_frames(vc, hint, rounds, tail):
     """Descriptor batches with the uniform length hint, as bench.py's cfg4
     slices: the file's last frame (816 B) and an empty frame among the tail
     frames, frame starts unaligned (odd gaps), one frame longer than the hint
-    (its front piece absorbs the excess)."""
+    (its front piece absorbs the excess). The 8-round batch (8 GiB) is the
+    suite's case of the one-word dynamic-tail queue, asserted from the plan;
+    it also sends payload states through that queue (verify_frames_ex on the
+    same buffer, whose trailers are random bytes: nearly every frame is bad,
+    and every frame gets its state)."""
     G = vc.lanes_per_frame(hint)
     n = _waves() * (64 // G) * rounds + tail
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    plan = vc.plan_frames(cus, n, hint, descriptors=True)
+    assert plan[0].qparts == (1 if rounds == 8 else 0), plan[0].astuple()
+    if rounds == 8:
+        assert plan[0].static_rounds >= 1 and plan[0].static_rounds < rounds
     rng = np.random.default_rng(hint + tail)
     lens = np.full(n, hint, np.uint32)
     lens[-1] = 816
@@ -135,6 +144,21 @@ def test_descriptor_tail_short_and_empty_frames(vc, hint, rounds, tail):
     want, want_h = _oracle.frames(host, offs, lens, header=True, nthreads=16)
     assert np.array_equal(_u32(on), want) and np.array_equal(_u32(off), want)
     assert np.array_equal(_u32(hon), want_h) and np.array_equal(_u32(hoff), want_h)
+    if rounds != 8:
+        return
+    # payload states out of the one-word queue (k_frames<16, 1, true>; its last 41 frames from a second launch)
+    from tests.test_gpu_dyn_queue import _want_states
+
+    plan = vc.plan_frames(cus, n, hint, descriptors=True, want_payload=True)
+    assert len(plan) == 2 and plan[0].qparts == 1 and plan[0].static_rounds >= 1, [l.astuple() for l in plan]
+    del on, off, hon, hoff
+    pay = torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device=DEV)
+    ok, nbad, _ = vc.verify_frames_ex(buf, off=d_off, length=d_len, len_hint=hint, out_pay=pay)
+    torch.cuda.synchronize()
+    states, _ = _want_states(host, offs, lens)
+    want_ok, want_bad = _oracle.verify_frames(host, offs, lens, nthreads=16)
+    assert np.array_equal(_u32(pay), states)
+    assert int(nbad.item()) == want_bad and np.array_equal(ok.cpu().numpy(), want_ok)
 
 
 def test_verify_tail_with_corruption(vc):

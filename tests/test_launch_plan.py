@@ -468,6 +468,34 @@ def test_plan(knobs, cid, args, kn):
     assert [l[4] for l in got] == [0, got[0][5] if got else 0][:len(got)]
 
 
+@pytest.mark.parametrize("cus", [64, 128, 256, 304])
+def test_gpu_queue_shapes_reach_the_queue(knobs, cus):
+    """The shapes of tests/test_gpu_dyn_queue.py are functions of the CU count; each GPU case asserts
+    from the plan that it reaches its branch (the 64 partitions with a round of the machine behind the
+    static rounds, the second launch of a re-cut tail, more ragged items than waves). The same
+    assertions here, for the device sizes the suite may meet."""
+    from tests import test_gpu_dyn_queue as q
+
+    knobs()
+    n1, plan = q.plan_case1(vc, cus)
+    assert (plan[0].qparts, plan[0].static_rounds, plan[0].depth, len(plan)) == (64, 4, -3, 2)
+    n2, plan = q.plan_case2(vc, cus)
+    assert n2 == n1 and (plan[0].qparts, plan[0].static_rounds, plan[0].depth) == (64, 4, 1)
+    _, plans = q.plan_case3(vc, cus)
+    assert [plans[k][0].depth for k in (-1, 1, 0, "pay")] == [-2, 1, 0, 1]
+    assert all(p[0].qparts == 64 and p[0].static_rounds == 4 for p in plans.values())
+    n4, plan = q.plan_case4(vc, cus)
+    assert (plan[0].qparts, plan[0].static_rounds, plan[0].lanes) == (64, 24, 8) and n4 * 4100 < 8 << 30
+    for G in (2, 4, 8, 16, 32):
+        n5, plan = q.plan_case5(vc, cus, G)
+        assert plan[0].qparts == 0 and plan[1].first == cus * 16 * (64 // G) * 2 and plan[1].count == 100
+    q.plan_case6(vc, cus)
+    _, plan = q.plan_case7(vc, cus)
+    assert plan[0].lanes == 8 and plan[1].count == 77
+    # and the knobs are back where the table assumes them
+    assert vc.plan_frames(256, _rounds(2, 8), 600, descriptors=True)[0].astuple() == EXPECTED["u600d-r8"][0]
+
+
 # ---- the window calls (val_gpu_plan_window) ----------------------------------
 # The lanes and grids of the framer, both unpack calls, the scan and the fill,
 # pinned the same way: W_EXPECTED holds what the launch functions computed

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import _oracle
+from tests import _split_shapes as shapes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -43,6 +44,25 @@ def _planned_tail(vc, n, typical_len, descriptors=False):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     plan = vc.plan_frames(cus, n, typical_len, descriptors=descriptors, flen=0 if descriptors else typical_len)
     return [l.tail_n for l in plan]
+
+
+def _off_run_is_split(vc, n, typical_len, tail, descriptors=False):
+    """With the path off the tail frames are a second launch. Whether the planner gives that launch to
+    k_frames_split at this device's CU count: asserted equal to the rule restated in
+    tests/_split_shapes.py, with the launch's first frame, count, chunk size and grid."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    with shapes.tail_pieces_off(vc):
+        plan = vc.plan_frames(cus, n, typical_len, descriptors=descriptors, flen=0 if descriptors else typical_len)
+    rows = [l.astuple() for l in plan]
+    if len(plan) == 1:  # a tail that would not fit one round at twice the lanes stays in the one launch
+        assert plan[0].count == n and plan[0].tail_n == 0 and -(-tail // (32 // plan[0].lanes)) > _waves(), rows
+        return False, cus
+    assert len(plan) == 2 and plan[1].first == plan[0].count == n - tail and plan[1].count == tail, rows
+    split = plan[1].kernel == vc.KERNEL_SPLIT
+    assert split == shapes.rule_says_split(cus, tail, typical_len), rows
+    if split:
+        assert plan[1].k0 == shapes.k0_for(typical_len) and plan[1].grid == min(tail, cus), rows
+    return split, cus
 
 
 def _run_both(vc, fn):
@@ -88,6 +108,10 @@ def test_strided_tail_every_frame(vc, flen, rounds, tail):
     on, off, used = _run_both(vc, fn)
     assert used == 1
     assert _planned_tail(vc, n, flen) == [tail]
+    # the off-run's second launch: k_frames_split on 256 CUs for every case but the 777 frames of 24,580 B
+    # (4 trips x 3 round-times against 7 rounds), which k_frames hashes at 64 lanes
+    split, cus = _off_run_is_split(vc, n, flen, tail)
+    assert cus != 256 or split == (flen != 24580)
     host = buf.cpu().numpy()
     want, want_h = _oracle.frames_strided(host, stride, flen, n, header=True, nthreads=16)
     assert np.array_equal(_u32(on), want)
@@ -140,6 +164,8 @@ def test_descriptor_tail_short_and_empty_frames(vc, hint, rounds, tail):
     (on, hon), (off, hoff), used = _run_both(vc, fn)
     assert used == 1
     assert _planned_tail(vc, n, hint, descriptors=True) == [tail]
+    split, _ = _off_run_is_split(vc, n, hint, tail, descriptors=True)  # the off-run's second launch
+    assert split or cus != 256
     host = buf.cpu().numpy()
     want, want_h = _oracle.frames(host, offs, lens, header=True, nthreads=16)
     assert np.array_equal(_u32(on), want) and np.array_equal(_u32(off), want)
@@ -187,6 +213,8 @@ def test_verify_tail_with_corruption(vc):
 
     (ok_on, nb_on), (ok_off, nb_off), used = _run_both(vc, fn)
     assert used == 1
+    split, cus = _off_run_is_split(vc, n, flen, tail)  # the off-run verifies the 57 tail frames in k_frames_split
+    assert split or cus != 256
     want_ok = np.ones(n, np.uint8)
     want_ok[bad] = 0
     assert nb_on == nb_off == bad.size
@@ -268,6 +296,8 @@ def test_tail_fuzz(vc):
             want, want_h = _oracle.frames(host, offs, lens, header=True, nthreads=16)
         (on, hon), (off_, hoff), used = _run_both(vc, fn)
         used_total += used
+        split, _ = _off_run_is_split(vc, n, flen, tail, descriptors=not strided)
+        case += " off-run tail on split" if split else " off-run tail on k_frames"
         assert np.array_equal(_u32(on), want) and np.array_equal(_u32(off_), want), case
         assert np.array_equal(_u32(hon), want_h) and np.array_equal(_u32(hoff), want_h), case
         # verify: trailers from the oracle, one tail frame with a flipped bit

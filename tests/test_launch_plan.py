@@ -496,6 +496,78 @@ def test_gpu_queue_shapes_reach_the_queue(knobs, cus):
     assert vc.plan_frames(256, _rounds(2, 8), 600, descriptors=True)[0].astuple() == EXPECTED["u600d-r8"][0]
 
 
+@pytest.mark.parametrize("cus", [64, 128, 256, 304])
+def test_gpu_split_shapes_reach_split(knobs, cus):
+    """The shapes of tests/test_gpu_split.py and tests/test_gpu_split_edges.py are functions of the CU
+    count (tests/_split_shapes.py); each GPU case asserts from the plan that its call is a
+    k_frames_split launch with the expected chunk size, grid and first frame. The same assertions
+    here, with the properties the shape functions assert of their own batches (a bad frame in every
+    trip, every length at every phase, what the fuzz rounds reached at the default seed), for the
+    device sizes the suite may meet."""
+    from tests import _split_shapes as s
+
+    knobs()
+    # the cases of tests/test_gpu_split.py
+    for n, payload in ((1, 8192), (3, 16384), (17, 16384), (256, 65516), (64, 65520)):
+        s.split_plan(vc, cus, n, 16 + payload, k0=s.STRIDED_K0[payload])
+    for hint, k0 in ((8192, 10), (16400, 11), (65532, 12)):
+        s.split_plan(vc, cus, min(200, cus), hint, descriptors=True, k0=k0)
+    s.split_plan(vc, cus, 120, 32784, k0=12)
+    s.split_plan(vc, cus, 1, 8192, k0=10)
+    assert s.not_split_plan(vc, cus, 1, 8191)[0].kernel == vc.KERNEL_FRAMES_C0
+    # 300 frames of 8,192 B: one trip of the grid or none
+    assert s.rule_says_split(cus, 300, 8192) == (cus >= 300)
+    if cus == 256:
+        s.not_split_plan(vc, cus, 300, 8192)
+    if cus == 304:
+        s.split_plan(vc, cus, 300, 8192, k0=10)
+    # 1. three trips
+    for desc in (False, True):
+        n, plan = s.trips_plan(vc, cus, desc)
+        assert (n, plan[0].grid, plan[0].k0) == (2 * cus + 3, cus, 12)
+    lens, offs, total = s.trips_descriptors(cus)
+    assert lens.size == 2 * cus + 3 and total < 64 << 20
+    bad = s.trips_bad(cus, lens)
+    assert all(0 <= s.bad_position(k, int(lens[f]), s.TRIPS_K0) < int(lens[f]) + 4 for f, k in bad)
+    assert all(s.bad_position(k, int(lens[f]), s.TRIPS_K0) < int(lens[f]) for f, k in bad if k in (0, 1, 6))
+    # 2. the ladder, the edges, the long frame
+    assert [s.ladder_plan(vc, cus, i)[0] for i in range(len(s.LADDER))] == [f for f, _ in s.LADDER]
+    assert [k for _, k in s.LADDER] == [10, 11, 12, 13, 14, 16, 17, 20, 21] == [s.k0_for(f) for f, _ in s.LADDER]
+    for hint, k0 in s.EDGE_HINTS:
+        lens, offs, total = s.edge_descriptors(k0)
+        W = 1 << k0
+        assert lens.size == 288 and total < 64 << 20
+        for m in s.EDGE_M:
+            for r in (0, 1, 3, 4, 63, 64, 65, W - 1):
+                assert set(int(o) % 4 for o, L in zip(offs, lens) if L == m * W + r) == {0, 1, 2, 3}, (m, r)
+        assert set(int(c) for c in s.chunks(lens, k0)) >= {1, 15, 16, 17, 32, 33, 49}
+        calls = s.edge_calls(vc, cus, hint, k0)
+        assert calls[0][0] == 0 and calls[-1][1] == 288 and all(a[1] == b[0] for a, b in zip(calls, calls[1:]))
+        assert len(calls) == (-(-288 // cus) if hint == 8192 else 1)
+    s.big_plan(vc, cus)
+    # 3. split as the second launch, with the tail pieces off
+    with s.tail_pieces_off(vc):
+        for tail in s.tail_counts(cus):
+            for desc in (False, True):
+                n, plan = s.tail_plan(vc, cus, tail, desc)
+                assert (plan[1].first, plan[1].count, plan[1].k0) == (cus * 64, tail, 12)
+                assert -(-tail // plan[1].grid) == (1 if tail == 6 else 2)
+            lens, offs, total = s.tail_descriptors(cus, tail)
+            assert lens.size == cus * 64 + tail and sorted(set(s.tail_bad(cus, tail))) == s.tail_bad(cus, tail)
+    # with them on, the same batches are one launch with the tail inside it
+    assert [l.tail_n for l in vc.plan_frames(cus, cus * 64 + 6, 65532, flen=65532)] == [6]
+    # 4. the fuzz at its default seed and rounds: every round on split, and what the rounds must reach
+    rounds = s.fuzz_rounds(vc, cus, s.FUZZ_DEFAULT_SEED, s.FUZZ_DEFAULT_ROUNDS)
+    assert len(rounds) == 60
+    for c in rounds:
+        s.split_plan(vc, cus, c["n"], c["typical"], descriptors=c["descriptors"], k0=c["k0"])
+        assert 1 <= c["n"] <= 3 * cus and 8192 <= c["typical"] <= 1 << 21 and c["total"] <= 64 << 20
+        assert c["k0"] == s.k0_for(c["typical"]) and c["trips"] == -(-c["n"] // min(c["n"], cus))
+    s.fuzz_coverage(rounds)
+    # and the knobs are back where the table assumes them
+    assert vc.plan_frames(256, 16384 + 6, 65532, flen=65532)[0].astuple() == EXPECTED["tail-s65532-r1+6"][0]
+
+
 # ---- the window calls (val_gpu_plan_window) ----------------------------------
 # The lanes and grids of the framer, both unpack calls, the scan and the fill,
 # pinned the same way: W_EXPECTED holds what the launch functions computed

@@ -448,11 +448,15 @@ def binned_always(vc):
     vc.set_ragged_min_frames(1)
 
 
+def _prefilled(n, dev, dtype=torch.int32):
+    return torch.full((n,), 0xA5 if dtype == torch.uint8 else -0x5A5A5A5B, dtype=dtype, device=dev)
+
+
 def _run_ragged(vc, dev, base, offs, lens, header=False):
     vc.set_geometry()  # automatic geometry: len_hint == 0 selects the binned path
     d = torch.from_numpy(base).to(dev)
-    crc = torch.empty(offs.size, dtype=torch.int32, device=dev)
-    hdr = torch.empty(offs.size, dtype=torch.int32, device=dev) if header else None
+    crc = _prefilled(offs.size, dev)  # 0xA5 bytes: a frame that no item covers cannot show a recycled value
+    hdr = _prefilled(offs.size, dev) if header else None
     vc.frames(d, off=torch.from_numpy(offs.view(np.int64)).to(dev),
               length=torch.from_numpy(lens.view(np.int32)).to(dev), out_crc=crc, out_hdr=hdr, len_hint=0)
     torch.cuda.synchronize()
@@ -494,9 +498,11 @@ def test_ragged_every_length_and_verify(vc, dev, binned, monkeypatch):
     base = _with_trailers(base, offs, lens)
     base[int(offs[1234]) + 3] ^= 0x40
     ok, nbad = vc.verify_frames(torch.from_numpy(base).to(dev), off=torch.from_numpy(offs.view(np.int64)).to(dev),
-                                length=torch.from_numpy(lens.view(np.int32)).to(dev), len_hint=0)
+                                length=torch.from_numpy(lens.view(np.int32)).to(dev), len_hint=0,
+                                out_ok=_prefilled(lens.size, dev, torch.uint8))
     torch.cuda.synchronize()
     assert int(nbad.item()) == 1 and int(ok.cpu().numpy().argmin()) == 1234
+    assert int(ok.cpu().numpy().sum()) == lens.size - 1
 
 
 def test_empty_batches(vc, dev):

@@ -59,8 +59,9 @@ def _shuffled(seed, n, L, gap_max=7, first_at_zero=True):
 
 def _frames(vc, dev, base, offs, lens, hint, header=True):
     d = torch.from_numpy(base).to(dev)
-    crc = torch.empty(offs.size, dtype=torch.int32, device=dev)
-    hdr = torch.empty(offs.size, dtype=torch.int32, device=dev) if header else None
+    # 0xA5 bytes: a frame that a launch skips cannot show the value an earlier call left in recycled memory
+    crc = torch.full((offs.size,), -0x5A5A5A5B, dtype=torch.int32, device=dev)
+    hdr = torch.full((offs.size,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if header else None
     vc.frames(d, off=torch.from_numpy(offs.view(np.int64)).to(dev), length=torch.from_numpy(lens.view(np.int32)).to(dev),
               out_crc=crc, out_hdr=hdr, len_hint=hint)
     torch.cuda.synchronize()

@@ -10,6 +10,7 @@ hand from that code below. A row is a launch as
 (kernel, lanes, depth, grid, first, count, k0, qparts, static_rounds,
  tail_n, tail_k0, tail_units), kernel 0 ragged, 1 split, 2 k_frames,
 3 k_frames with one-pass loads."""
+import numpy as np
 import pytest
 
 import val_protocol_amd.crc as vc
@@ -566,6 +567,108 @@ def test_gpu_split_shapes_reach_split(knobs, cus):
     s.fuzz_coverage(rounds)
     # and the knobs are back where the table assumes them
     assert vc.plan_frames(256, 16384 + 6, 65532, flen=65532)[0].astuple() == EXPECTED["tail-s65532-r1+6"][0]
+
+
+@pytest.fixture(scope="module")
+def ragged_trips():
+    """The 4.5 M lengths of the binning-trips case: no function of the CU count, built once."""
+    from tests import _ragged_shapes as s
+
+    return s.trips_batch()
+
+
+def test_ragged_restatement_matches_the_header_table():
+    """tests/_ragged_shapes.py restates length_bucket from the table in the comment above it: the
+    ranges 0..7 | 8..36 | 37..117 | 118..134 and 135, the class limits, and each bucket's lowest
+    and highest length, checked against each other over every length up to 70,000."""
+    from tests import _ragged_shapes as s
+
+    L = np.arange(0, 70001)
+    b = s.bucket(L)
+    assert np.array_equal(s.bucket_class(b), s.length_class(L)) and (np.diff(b) >= 0).all()
+    assert [int(b[L == v][0]) for v in (0, 128, 129, 1023, 1024, 1025, 8191, 8192, 8193, 49151, 49152, 49153, 65536,
+                                        65537)] == [0, 0, 1, 7, 8, 9, 36, 37, 38, 117, 118, 119, 134, 135]
+    assert s.bucket(2**32 - 1) == 135 and s.bucket((1 << 24) + 5) == 135
+    for k in range(s.BUCKETS):
+        lo, hi = s.bucket_bounds(k)
+        assert lo == int(L[b == k].min()) and (hi if hi is not None else 70000) == int(L[b == k].max()), k
+    # rounds of the class: a bucket of class c spans LANES[c] * 64 bytes
+    for c in range(4):
+        for k in range(s.CLASS_FIRST_BUCKET[c] + 2, s.CLASS_FIRST_BUCKET[c + 1] - 1):
+            lo, hi = s.bucket_bounds(k)
+            assert hi is None or hi - lo + 1 == 64 * s.LANES[c], k
+    assert s.bin_grid(1) == (1, 1, 1) and s.bin_grid(2048) == (1, 2048, 1) and s.bin_grid(2049) == (2, 1025, 1)
+    assert s.bin_grid(262144) == (128, 2048, 1) and s.bin_grid(1 << 21) == (1024, 2048, 1)
+    assert s.bin_grid((1 << 21) + 1) == (1024, 2049, 2)
+    tab = s.class_table(np.array([5, 70000, 1024, 1023, 8192, 8192, 49152], np.uint32))
+    assert (tab["count"], tab["start"], tab["items"], tab["first_item"], tab["total"], tab["one_bucket"]) == \
+        ([2, 1, 2, 2], [5, 4, 2, 0], [1, 1, 1, 1], [3, 2, 1, 0], 4, False)
+    assert [s.item_class(tab, it) for it in range(4)] == [3, 2, 1, 0]
+
+
+@pytest.mark.parametrize("cus", [64, 128, 256, 304])
+def test_gpu_ragged_shapes_reach_their_branches(knobs, cus, ragged_trips):
+    """The shapes of tests/test_gpu_ragged_edges.py and tests/test_gpu_ragged_fuzz.py are functions of
+    the CU count (tests/_ragged_shapes.py); each GPU case asserts from the restated plan and from
+    val_gpu_plan_frames that it reaches its branch. The same assertions here for the device sizes
+    the suite may meet, and ragged_grid against the planner around the point where the grid reaches
+    the CU count."""
+    from tests import _ragged_shapes as s
+
+    knobs(ragged_min=1)
+    for n in [1, 2, 3, 4, 5, 47, 48, 49, 60, 61, 64 * 63 - 16, 64 * 63 - 15, 64 * 64 - 16, 64 * 64 - 15, 5000] + \
+            [64 * cus + d for d in (-80, -17, -16, -15, -13, -12, 0, 1, 64, 5000)] + [1 << 20, s.TRIPS_N]:
+        for pay in (False, True):
+            assert s.ragged_plan(vc, cus, n, want_payload=pay) == s.ragged_grid(cus, n)
+    assert s.ragged_grid(cus, 64 * cus - 16) == cus and s.ragged_grid(cus, 64 * cus - 80) == cus - 1
+    # 1. the binning loop's later trips
+    lens, plants = ragged_trips
+    assert s.ragged_plan(vc, cus, lens.size) == cus and len(plants) == 9
+    assert all(int(lens[i]) == L for i, L in plants.items())
+    # 2. every bucket
+    lens, offs, total, bad = s.every_bucket_batch()
+    assert s.ragged_plan(vc, cus, lens.size, want_payload=True) == 5 and s.class_table(lens)["total"] == 1 + 4 + 21 + 10
+    # 3. class subsets and partial items
+    seen = set()
+    for si, classes in enumerate(s.SUBSETS):
+        lens, offs, total, tab, bad = s.subset_batch(si)
+        grid = s.ragged_plan(vc, cus, lens.size)
+        assert s.parts(grid) == grid <= 4 and total < 2 << 20
+        assert [tab["count"][c] for c in classes] == [s.count_of(c, s.subset_kind(si, j)) for j, c in enumerate(classes)]
+        assert len(bad) == sum(1 + (tab["items"][c] > 1) for c in classes)
+        seen |= {(c, s.subset_kind(si, j)) for j, c in enumerate(classes)}
+    assert seen == {(c, k) for c in range(4) for k in range(s.COUNT_KINDS)}, "every class at every count"
+    # 4. one bucket at a small grid and at the full grid
+    grids = [s.identity_small_facts(cus, n, L) for n, L in s.IDENTITY_SMALL]
+    assert [g for g, _ in grids] == [1, 1, 1, 3, 16, 18, 2] and [i for _, i in grids] == [1, 1, 2, 4, 32, 35, 7]
+    n = s.identity_full_n(cus)
+    assert s.ragged_plan(vc, cus, n) == cus
+    assert [s.ragged_plan(vc, cus, k) for k in s.CHAIN_N] == [63, 15, 16] and s.CHAIN_N[1] * 4 < s.CHAIN_N[0]
+    assert all(s.mixed_lens(k, i).size == k for i, k in enumerate(s.CHAIN_N[:2]))
+    # 5. the deep queue, and its host chunks on the default threshold
+    lens, offs, total, tab, bad, chunks = s.deep_batch(cus)
+    assert s.ragged_plan(vc, cus, lens.size) == cus and tab["total"] >= 4 * 16 * cus
+    knobs()
+    for i, j in chunks:
+        assert j - i >= 4096 and int(offs[j - 1]) + int(lens[j - 1]) - int(offs[i]) <= s.HOST_CHUNK
+        assert s.ragged_plan(vc, cus, j - i) == s.ragged_grid(cus, j - i)
+    assert chunks[0][0] == 0 and chunks[-1][1] == lens.size and all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+    knobs(ragged_min=1)
+    # 6. both reservation paths
+    assert s.slot_facts(8192) == (4, 2048, 1, 64) and s.slot_facts(8192 - 37) == (4, 2039, 1, 54)
+    for n in (8192, 8192 - 37):
+        lens, uniform = s.slot_batch(n)
+        assert s.ragged_plan(vc, cus, n) == min(cus, 129 - (n < 8192)) and 40 <= sum(uniform) <= 44 and uniform[-1]
+    # 7. the fuzz at its default seed and rounds
+    rounds = s.fuzz_rounds(cus, s.FUZZ_DEFAULT_SEED, s.FUZZ_DEFAULT_ROUNDS)
+    assert len(rounds) == 60
+    for r in rounds:
+        assert s.ragged_plan(vc, cus, r["n"], want_payload=r["mode"] == "ex") == r["grid"]
+        assert 1 <= r["n"] <= s.FUZZ_MAX_N and int(r["lens"].astype(np.int64).sum()) <= s.FUZZ_CAP
+    s.fuzz_coverage(rounds, cus)
+    # and the knobs are back where the table assumes them
+    knobs()
+    assert vc.plan_frames(256, 262144, 0, descriptors=True)[0].astuple() == EXPECTED["cfg5"][0]
 
 
 # ---- the window calls (val_gpu_plan_window) ----------------------------------

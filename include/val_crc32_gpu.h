@@ -683,6 +683,15 @@ val_status_t val_gpu_host_copy_probe(uint32_t copies, uint64_t bytes, uint32_t r
  * used it. */
 void val_gpu_set_tail_pieces(int enable);
 uint64_t val_gpu_tail_piece_launches(void);
+/* Multi-pass launches of long frames (8 lanes per frame, frames of 8 KiB and
+ * more, no payload states) read every round after a frame's first through
+ * non-temporal LDS-DMA beside a compact table image, instead of ordinary
+ * loads. 1 / 0 force the path on (for every launch its kernels can hash,
+ * one-pass launches included) / off, -1 = VAL_GPU_STREAM_LOADS (unset: the
+ * rule). Speed only; results never change. _launches counts the launches that
+ * used it. */
+void val_gpu_set_stream_loads(int enable);
+uint64_t val_gpu_stream_load_launches(void);
 /* Wire bytes per H2D chunk of the *_frames_host calls; 0 = default (64 MiB).
  * Device memory use is two chunks. Speed and memory only; results never change. */
 val_status_t val_gpu_set_host_chunk_bytes(size_t bytes);
@@ -739,6 +748,11 @@ typedef struct val_gpu_launch {
 } val_gpu_launch_t;
 uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
                              uint32_t last_len, int want_payload, val_gpu_launch_t out_plan[2]);
+/* The load path of each of those launches, same arguments: out_stream[i] = 1
+ * where launch i reads through LDS-DMA (val_gpu_set_stream_loads), else 0.
+ * Returns the number of launches. */
+uint32_t val_gpu_plan_stream_loads(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
+                                   uint32_t last_len, int want_payload, int out_stream[2]);
 /* The launches one window call would make after its verify launches, if any
  * (those are val_gpu_plan_frames), in order, with the process's current knobs
  * (forced lanes, scan front); of a launch, kernel, lanes, grid and count (the

@@ -60,6 +60,7 @@ EXPORTS = (
     "val_gpu_host_batch_min_bytes_for",
     "val_gpu_cpu_batch_count", "val_gpu_set_host_cpu_threads", "val_gpu_host_multi_min_bytes", "val_gpu_host_multi_min_bytes_ex",
     "val_gpu_set_tail_pieces", "val_gpu_tail_piece_launches", "val_gpu_plan_frames", "val_gpu_plan_window",
+    "val_gpu_set_stream_loads", "val_gpu_stream_load_launches", "val_gpu_plan_stream_loads",
     "val_batch_attach", "val_batch_flush", "val_batch_get_stats", "val_batch_detach", "val_batch_crc32_provider",
     "val_serialize_handshake", "val_deserialize_handshake", "val_serialize_meta", "val_deserialize_meta",
     "val_serialize_resume_resp", "val_deserialize_resume_resp", "val_serialize_verify_request",
@@ -192,6 +193,9 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
     fn("val_gpu_host_multi_min_bytes_ex", u64, ctypes.c_int, ctypes.c_int, u64)
     fn("val_gpu_set_tail_pieces", None, ctypes.c_int)
     fn("val_gpu_tail_piece_launches", u64)
+    fn("val_gpu_set_stream_loads", None, ctypes.c_int)
+    fn("val_gpu_stream_load_launches", u64)
+    fn("val_gpu_plan_stream_loads", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(ctypes.c_int))
     fn("val_frame_data_batch_dev", i32, _vp, _vp, _vp, _vp, _vp, u32, _vp, _vp, u64, u32, _vp, _vp, _vp, _vp, _vp)
     fn("val_frame_data_layout", i32, _vp, _vp, u32, _vp, _vp, ctypes.POINTER(u64))
     fn("val_frame_unpack_work_bytes", u64, u32)
@@ -446,6 +450,25 @@ def plan_frames(cus: int, n: int, typical_len: int, *, descriptors: bool = False
     k = lib().val_gpu_plan_frames(cus, n, int(descriptors), typical_len, flen, flen if last_len is None else last_len,
                                   int(want_payload), out)
     return [out[i] for i in range(k)]
+
+
+def plan_stream_loads(cus: int, n: int, typical_len: int, *, descriptors: bool = False, flen: int = 0,
+                      last_len: Optional[int] = None, want_payload: bool = False) -> list:
+    """For each launch of plan_frames (same arguments): True where it reads
+    through LDS-DMA (set_stream_loads). Needs no GPU."""
+    out = (ctypes.c_int * 2)()
+    k = lib().val_gpu_plan_stream_loads(cus, n, int(descriptors), typical_len, flen,
+                                        flen if last_len is None else last_len, int(want_payload), out)
+    return [bool(out[i]) for i in range(k)]
+
+
+def set_stream_loads(enable: int) -> None:
+    """1 / 0: force the LDS-DMA load path of long frames on / off; -1: the rule."""
+    lib().val_gpu_set_stream_loads(int(enable))
+
+
+def stream_load_launches() -> int:
+    return int(lib().val_gpu_stream_load_launches())
 
 
 def plan_window(call: int, cus: int, n: int, *, groups: int = 0, max_frames: int = 0, len_hint: int = 0) -> list:

@@ -107,6 +107,77 @@ __device__ __forceinline__ uint32_t byte_step(uint32_t c, uint32_t byte, const S
     return lds_read(tab_addr(c ^ byte, b.t1, 0) + 128u) ^ (c >> 8);
 }
 
+// ---- compact image of the stream-load instances (k_frames_stream) -----------------
+//   [0, 64 KiB)        slice tables, 16 bank replicas: row = byte value * 256 B
+//                      holds T3|T2|T1|T0 as four 64-B slots (slot s = T_{3-s},
+//                      which consumes byte s of a word).
+//   [64 KiB, 128 KiB)  the LDS-DMA ring: one 4 KiB batch per wave.
+//   [128 KiB, ...)     the maps, where every kernel has them.
+// XOR commutes, so the four lookups of a word may run in a different order in
+// different lanes: lanes with bit 4 clear look up slots 0,1,2,3, the others
+// 1,0,3,2. In every ds_read_b32 one half of each 32-lane half-wave is then in
+// banks 0-15 and the other in banks 16-31: conflict-free for any data with
+// half the replicas (tests/test_stream_grid_model.py; measured in
+// bench/micro/mb16.hip). The address is still one v_perm_b32, with a per-lane
+// selector register.
+// These lookups are asm statements, each holding its reads and their wait:
+// the tables and the ring are one array to hipcc, which would wait vmcnt(0)
+// for the batch in flight before every table read.
+constexpr uint32_t kLdsRing = 65536, kRingBatch = 4096;
+struct RotBases {
+    uint32_t a, b;    // row offsets of the slots lookups 0 and 1 read (lookups 2 and 3: 128 B above)
+    uint32_t sel[4];  // v_perm selectors: the byte each lookup consumes
+};
+
+__device__ __forceinline__ RotBases rot_bases(int lane)
+{
+    const uint32_t lo = (uint32_t)(lane & 15) << 2, c = (uint32_t)(lane >> 4) & 1u;
+    RotBases r;
+    r.a = c * 64u + lo;
+    r.b = (1u - c) * 64u + lo;
+    r.sel[0] = 0x0C020400u + (c << 8);
+    r.sel[1] = 0x0C020400u + ((1u - c) << 8);
+    r.sel[2] = 0x0C020400u + ((2u + c) << 8);
+    r.sel[3] = 0x0C020400u + ((3u - c) << 8);
+    return r;
+}
+
+__device__ __forceinline__ uint32_t s4_step(uint32_t c, uint32_t w, const RotBases &b)
+{
+    const uint32_t y = c ^ w;
+    const uint32_t a0 = __builtin_amdgcn_perm(y, b.a, b.sel[0]), a1 = __builtin_amdgcn_perm(y, b.b, b.sel[1]),
+                   a2 = __builtin_amdgcn_perm(y, b.a, b.sel[2]), a3 = __builtin_amdgcn_perm(y, b.b, b.sel[3]);
+    uint32_t r0, r1, r2, r3;
+    // volatile, "memory": never above the prologue's LDS fill and barrier
+    asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %5\n\tds_read_b32 %2, %6 offset:128\n\t"
+                 "ds_read_b32 %3, %7 offset:128\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+                 : "v"(a0), "v"(a1), "v"(a2), "v"(a3)
+                 : "memory");
+    return r0 ^ r1 ^ r2 ^ r3;
+}
+
+// T0 is slot 3; any replica serves (rare: tails, tiny frames).
+__device__ __forceinline__ uint32_t byte_step(uint32_t c, uint32_t byte, const RotBases &b)
+{
+    return lds_read(tab_addr(c ^ byte, (b.a & 63u) | 192u, 0)) ^ (c >> 8);
+}
+
+// map_apply beside a DMA batch in flight (asm, as the lookups above).
+__device__ __forceinline__ uint32_t map_apply_dma(uint32_t a, uint32_t map)
+{
+    uint32_t ad[8], r[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) ad[k] = map + ((a >> (4 * k)) & 15u) * 4u;
+    asm volatile("ds_read_b32 %0, %8\n\tds_read_b32 %1, %9 offset:64\n\tds_read_b32 %2, %10 offset:128\n\t"
+        "ds_read_b32 %3, %11 offset:192\n\tds_read_b32 %4, %12 offset:256\n\tds_read_b32 %5, %13 offset:320\n\t"
+        "ds_read_b32 %6, %14 offset:384\n\tds_read_b32 %7, %15 offset:448\n\ts_waitcnt lgkmcnt(0)"
+        : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
+        : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
+        : "memory");
+    return r[0] ^ r[1] ^ r[2] ^ r[3] ^ r[4] ^ r[5] ^ r[6] ^ r[7];
+}
+
 // Advance register a by the distance of the nibble map at byte address
 // `map`: 8 lookups (table k holds the images of n << 4k).
 __device__ __forceinline__ uint32_t map_apply(uint32_t a, uint32_t map)
@@ -200,6 +271,43 @@ __device__ __forceinline__ void build_lds_tables(const uint32_t *consts)
     LdsImage im;
     lds_tables_issue(consts, im);
     lds_tables_write(im);
+}
+
+// The compact image's prologue, from the same blob and in the same two halves:
+// 4 table chunks and 2 map words per thread. Chunk c = r * 1024 + t is row
+// c >> 4 (the byte value), slot (c >> 2) & 3 -> T_{3 - slot}[byte].
+struct RotImage {
+    uint32_t v[4], vm[2];
+};
+
+__device__ __forceinline__ void lds_rot_issue(const uint32_t *consts, RotImage &im)
+{
+    const uint32_t t = threadIdx.x;
+    constexpr uint32_t kMapWords = kNumMaps * 128u;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t c = (uint32_t)r * kBlock + t;
+        im.v[r] = consts[kConstSlice + (3u - ((c >> 2) & 3u)) * 256u + (c >> 4)];
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const uint32_t i = (uint32_t)r * kBlock + t;
+        im.vm[r] = i < kMapWords ? consts[kConstGap + i] : 0u;
+    }
+}
+
+__device__ __forceinline__ void lds_rot_write(const RotImage &im)
+{
+    const uint32_t t = threadIdx.x;
+    constexpr uint32_t kMapWords = kNumMaps * 128u;
+    uint4 *lds4 = reinterpret_cast<uint4 *>(s_lds);
+#pragma unroll
+    for (int r = 0; r < 4; r++) lds4[(uint32_t)r * kBlock + t] = make_uint4(im.v[r], im.v[r], im.v[r], im.v[r]);
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const uint32_t i = (uint32_t)r * kBlock + t;
+        if (i < kMapWords) s_lds[kLdsMaps / 4u + i] = im.vm[r];
+    }
 }
 
 // The 16 maps "advance 2^(k0+i) bytes" into the LDS pow slots (2 words per

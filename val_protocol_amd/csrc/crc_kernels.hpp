@@ -21,6 +21,8 @@
 //   the other lanes own (gap step); a log2(G) __shfl_xor tree merges lanes.
 #pragma once
 
+#include <type_traits>
+
 #include "crc_device.hpp"
 
 namespace vcrc {
@@ -335,7 +337,8 @@ __device__ __forceinline__ void frame_desc(const FrameParams &p, uint64_t f, uin
 
 // Register after feeding words first..15 of w into a zero register
 // (first is wave-uniform: a scalar jump into the unrolled steps).
-__device__ __forceinline__ uint32_t s4_words_from(int first, const uint32_t (&w)[kWords], const SliceBases &sb)
+template <typename SB>
+__device__ __forceinline__ uint32_t s4_words_from(int first, const uint32_t (&w)[kWords], const SB &sb)
 {
     uint32_t acc = 0;
     switch (first) {
@@ -369,9 +372,9 @@ __device__ __forceinline__ uint32_t s4_words_from(int first, const uint32_t (&w)
 struct NoMid {
     __device__ void operator()() const {}
 };
-template <int GT, int PF, bool PAY, bool BF, bool C0 = false, typename Pre, typename Mid = NoMid>
+template <int GT, int PF, bool PAY, bool BF, bool C0 = false, typename SB, typename Pre, typename Mid = NoMid>
 __device__ __forceinline__ uint32_t hash_frame(const FrameParams &p, uint64_t f, bool active, uint64_t off, uint32_t L, int g,
-                                           const SliceBases &sb, int Gr, Pre &&pre, Mid &&mid = Mid{})
+                                           const SB &sb, int Gr, Pre &&pre, Mid &&mid = Mid{})
 {
     // PF < 0 (burst): rounds 1..-PF are all issued with round 0 and hashed in
     // place, never refilled; rounds past them (frames longer than the burst)
@@ -579,6 +582,190 @@ __device__ __forceinline__ uint32_t hash_frame(const FrameParams &p, uint64_t f,
     return acc;  // lane G - 1: the frame's raw register (before xorout)
 }
 
+// ---- stream loads: rounds >= 1 of long frames through nt LDS-DMA ---------------
+// The plain loop above sits on the roof of ordinary loads; an nt
+// LDS-DMA stream reads above it, and with the compact table image
+// (crc_device.hpp RotBases) there is room for a 4 KiB batch per wave beside
+// conflict-free tables (bench/micro/mb16.hip: +5.5% on cfg3's layout, HBM
+// traffic 1.000x the buffer against 1.015x).
+// Geometry: the unit grid ends at floor128(frame end), so every round after
+// round 0 is G / 2 whole 128-B lines of its frame. Round 0 (unit 0 from
+// inside the frame's first line, as above), the header words and the trailer
+// are ordinary loads issued at the group's start, where the ring is empty;
+// so is the tail line, the T <= 127 bytes past the grid, lane g taking its
+// 16-B piece g. Rounds >= 1: one batch of four glds dwordx4 per wave, each
+// instruction whole lines (1 KiB = 16 / G frames' rounds), a line in exactly
+// one instruction, per-lane source, wave-uniform lane-linear LDS destination.
+// Batch image: hash lane m's unit at 64 m, its 16-B piece k at position
+// (k + (m >> 2)) & 3, so each pass of the ds_read_b128 read-back touches 16
+// different bank quads. DMA instruction q, lane l writes 1024 q + 16 l, so it
+// fetches unit m = 16 q + (l >> 2), piece ((l & 3) - (l >> 4)) & 3.
+// The read-back waits vmcnt(0) (one batch in flight), the next batch is
+// issued into the same slots right after it, then the round is hashed; no
+// barrier: a wave reads only its own slot. Frames of one wave may differ in
+// their round counts: a DMA lane is predicated on its frame's count, a hash
+// lane keeps its register in rounds its frame does not have.
+// After the merge lane G - 1 feeds the tail, word steps then byte steps, the
+// words handed over by shuffles. tests/_stream_grid.py restates the geometry.
+template <int G, int PF, bool PAY>
+constexpr bool kStreamLoads = G == 8 && PF == 1 && !PAY;  // G = 16: not measured yet
+
+template <int G, typename Pre, typename Mid = NoMid>
+__device__ __forceinline__ uint32_t hash_frame_stream(const FrameParams &p, uint64_t f, bool active, uint64_t off, uint32_t L,
+                                                  int g, const RotBases &sb, Pre &&pre, Mid &&mid = Mid{})
+{
+    constexpr uint32_t kRound = (uint32_t)G * kUnit;
+    constexpr int kLog = ilog2(G);
+    const int lane = (int)__lane_id();
+    const uint32_t slot = kLdsRing + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kRingBatch;
+    gu8 *fp = gptr(p.base) + off;
+    const uint32_t seed = (f == 0) ? p.seed0 : p.seed_rest;
+    const uint32_t T = min((uint32_t)((uintptr_t)(fp + L) & 127u), L);
+    const uint32_t Lg = L - T;
+    const uint32_t U = Lg ? (Lg + kUnit - 1) / kUnit : 1u;
+    const uint32_t R = active ? (U + G - 1) >> kLog : 0u;
+    const uint32_t pad = U * kUnit - Lg;
+    const int u0 = (int)U - G * (int)R + g;
+    const bool tiny = u0 == 0 && Lg < 4;
+    const bool last = active && g == G - 1;
+    gu8 *const dummy = gptr(reinterpret_cast<const uint8_t *>(p.consts));
+    // ordinary loads, all at the group's start
+    uint32_t w0[kWords];
+    load_unit0<false, false>(w0, u0, fp, Lg, pad, dummy);
+    const bool hdr = R > 0 && u0 == 0 && p.out_hdr;
+    uint32_t h0, h1;
+    if (hdr && L >= 8) {
+        h0 = ld32(fp);
+        h1 = ld32(fp + 4);
+    }
+    u32x4u tl = {0, 0, 0, 0};
+    if (active && Lg >= 4 && 16u * (uint32_t)g < T) tl = *reinterpret_cast<gu32x4u *>(fp + Lg + 16 * g);
+    uint32_t trailer = 0;
+    if (last && p.verify) trailer = ld32(fp + L);
+    // this lane's DMA sources: the frame of hash lane m = 16 q + (lane >> 2)
+    const uint64_t E = (uint64_t)(uintptr_t)(fp + Lg);
+    const uint8_t *src[4];
+    uint32_t Rq[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int m = 16 * q + (lane >> 2), fl = m & ~(G - 1);
+        const uint64_t Eq = ((uint64_t)(uint32_t)__shfl((int)(E >> 32), fl) << 32) | (uint32_t)__shfl((int)(uint32_t)E, fl);
+        Rq[q] = (uint32_t)__shfl((int)R, fl);
+        src[q] = reinterpret_cast<const uint8_t *>((uintptr_t)(Eq - (uint64_t)(Rq[q] ? Rq[q] - 1u : 0u) * kRound +
+                                                               (uint32_t)(m & (G - 1)) * kUnit +
+                                                               16u * (uint32_t)(((lane & 3) - (lane >> 4)) & 3)));
+    }
+    uint32_t Rmax = R;
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) Rmax = max(Rmax, (uint32_t)__shfl_xor((int)Rmax, o));
+    Rmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)Rmax);
+    const uint32_t rd0 = slot + (uint32_t)lane * kUnit, rot = (uint32_t)(lane >> 2);  // piece k at rd0 + 16 ((k + rot) & 3)
+    auto issue = [&](uint32_t k) {  // round k's batch
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (k < Rq[q])
+                __builtin_amdgcn_global_load_lds((const void *)src[q],
+                                                 (__attribute__((address_space(3))) void *)((char *)s_lds + slot + q * 1024), 16, 0, 2);
+            src[q] += kRound;
+        }
+    };
+    int first = (R == 0 || u0 < 0) ? kWords : (u0 == 0 ? (int)(pad >> 2) : 0);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) first = min(first, __shfl_xor(first, o));
+    first = __builtin_amdgcn_readfirstlane(first);
+    pre();
+    if (Rmax > 1u) issue(1);
+    if (hdr) {
+        uint32_t h = seed;
+        if (L >= 8) {
+            h = s4_step(h, h0, sb);
+            h = s4_step(h, h1, sb);
+        } else {
+            for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
+        }
+        p.out_hdr[f] = h ^ p.xorout;
+    }
+    uint32_t acc = 0;
+    if (R > 0) {
+        if (u0 == 0 && Lg >= 4) unit0_line_shift(w0, fp, pad);
+        unit0_finish(w0, u0, Lg, pad, seed);
+        acc = s4_words_from(first, w0, sb);
+        if (tiny) {  // Lg < 4: state of all L bytes straight from the seed
+            acc = seed;
+            for (uint32_t i = 0; i < L; i++) acc = byte_step(acc, fp[i], sb);
+        }
+    }
+    mid();
+    const bool seed_spill = g == 0 && pad > kUnit - 4 && (int)U - G * (int)(R - 1) == 1;
+    for (uint32_t k = 1; k < Rmax; k++) {
+        u32x4u cur[4];
+        uint32_t rd[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; i++) rd[i] = rd0 + 16u * ((i + rot) & 3u);
+        asm volatile("s_waitcnt vmcnt(0)\n\t"
+                     "ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(cur[0]), "=&v"(cur[1]), "=&v"(cur[2]), "=&v"(cur[3])
+                     : "v"(rd[0]), "v"(rd[1]), "v"(rd[2]), "v"(rd[3])
+                     : "memory");
+        if (k + 1u < Rmax) issue(k + 1u);
+        if (k == 1 && seed_spill) cur[0].x ^= seed >> (8 * (kUnit - pad));
+        uint32_t a = map_apply_dma(acc, gap_map(kLog));
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            a = s4_step(a, cur[q].x, sb);
+            a = s4_step(a, cur[q].y, sb);
+            a = s4_step(a, cur[q].z, sb);
+            a = s4_step(a, cur[q].w, sb);
+        }
+        acc = k < R ? a : acc;
+    }
+#pragma unroll
+    for (int j = 0; j < kLog; j++) {
+        const uint32_t other = __shfl_xor(acc, 1 << j);
+        const bool right = (g >> j) & 1;
+        const uint32_t left = right ? other : acc;
+        acc = map_apply(left, tree_map(j)) ^ (right ? acc : other);
+    }
+    // the tail: whole words piece by piece, then the bytes of the last word
+    const uint32_t Tt = (active && Lg >= 4) ? T : 0u;
+    uint32_t Tmax = Tt;
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) Tmax = max(Tmax, (uint32_t)__shfl_xor((int)Tmax, o));
+    Tmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)Tmax);
+    const int g0 = lane & ~(G - 1);
+    for (uint32_t pc = 0; 16u * pc < Tmax; pc++) {
+        const uint32_t w[4] = {(uint32_t)__shfl((int)tl.x, g0 | (int)pc), (uint32_t)__shfl((int)tl.y, g0 | (int)pc),
+                               (uint32_t)__shfl((int)tl.z, g0 | (int)pc), (uint32_t)__shfl((int)tl.w, g0 | (int)pc)};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t a = s4_step(acc, w[j], sb);
+            acc = (16u * pc + 4u * (uint32_t)j + 4u <= Tt) ? a : acc;
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64((Tt & 3u) != 0u)) {
+        const int from = g0 | (int)(Tt >> 4);
+        const uint32_t c0 = (uint32_t)__shfl((int)tl.x, from), c1 = (uint32_t)__shfl((int)tl.y, from),
+                       c2 = (uint32_t)__shfl((int)tl.z, from), c3 = (uint32_t)__shfl((int)tl.w, from);
+        const uint32_t wi = (Tt >> 2) & 3u, w = wi == 0 ? c0 : wi == 1 ? c1 : wi == 2 ? c2 : c3;
+#pragma unroll
+        for (uint32_t j = 0; j < 3; j++) {
+            const uint32_t a = byte_step(acc, (w >> (8 * j)) & 255u, sb);
+            acc = j < (Tt & 3u) ? a : acc;
+        }
+    }
+    if (last) {
+        const uint32_t crc = acc ^ p.xorout;
+        if (p.out_crc) p.out_crc[f] = crc;
+        if (p.verify) {
+            const bool good = (crc == trailer);
+            if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
+            if (!good && p.nbad) atomicAdd(p.nbad, 1u);
+        }
+    }
+    return acc;
+}
+
 #ifdef VCRC_TIMING  // diagnostic builds only (tools/timing_cfg2.py): per-wave s_memrealtime stamps
 __device__ uint64_t g_vcrc_time[4096 * 4];
 __device__ uint32_t g_vcrc_info[4096];  // ragged: class << 16 | (L >> 6) of lane 0's frame in the wave's last item
@@ -663,8 +850,8 @@ __device__ __forceinline__ void tail_desc(const FrameParams &p, uint32_t t, uint
 template <int G, int PF, bool PAY>
 constexpr bool kTailPieces = (G == 8 || G == 16) && PF == 1 && !PAY;
 
-template <int G, int PF, bool C0>
-__device__ __forceinline__ void tail_pieces(const FrameParams &p, int lane, const SliceBases &sb)
+template <int G, int PF, bool C0, typename SB>
+__device__ __forceinline__ void tail_pieces(const FrameParams &p, int lane, const SB &sb)
 {
     constexpr int kGroups = 64 / G;
     const uint32_t total = p.tail_n * p.tail_units;
@@ -820,6 +1007,150 @@ __global__ __launch_bounds__(kBlock) void k_frames(const FrameParams p)
         uint64_t gb_n = 0, fd_n = 0, od_n = 0;
         uint32_t Ld_n = 0;
         hash_frame<G, PF, PAY, false, C0>(p, fd, fd < p.n, od, Ld, ql % G, sb, G, [] {}, [&] {
+            gb_n = dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(kn)) * kGroups;
+            fd_n = gb_n + (uint64_t)(ql / G);
+            if (fd_n < p.n) frame_desc(p, fd_n, od_n, Ld_n);
+        });
+        gb = gb_n;
+        fd = fd_n;
+        od = od_n;
+        Ld = Ld_n;
+    }
+    if constexpr (kTailPieces<G, PF, PAY>) {
+        if (p.tail_n) tail_pieces<G, PF, C0>(p, ql, sb);
+    }
+    VCRC_STAMP(2);
+    // Exits are counted per workgroup, after a barrier: one atomic per CU. One
+    // per wave (4,096 on one word, serialised at its atomic unit) added tens of
+    // microseconds to the end of short launches, where the waves all finish
+    // together.
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t out = atomicAdd(&p.qhead[kDynParts * 16u], 1u);
+        if (out == gridDim.x - 1u) {  // every wave is past its last dequeue
+            for (uint32_t i = 0; i < P; i++) atomicExch(&p.qhead[i * 16u], 0u);
+            atomicExch(&p.qhead[kDynParts * 16u], 0u);
+        }
+    }
+}
+
+template <int G, typename Pre>
+__device__ __forceinline__ void group_pass_stream(const FrameParams &p, uint64_t &f, uint64_t &off, uint32_t &L, uint64_t &fb,
+                                                  uint64_t step, int lane, const RotBases &sb, Pre &&pre)
+{
+    const uint64_t fn = f + step;
+    uint64_t off_n = 0;
+    uint32_t L_n = 0;
+    if (fn < p.n) frame_desc(p, fn, off_n, L_n);
+    hash_frame_stream<G>(p, f, f < p.n, off, L, lane % G, sb, pre);
+    f = fn;
+    off = off_n;
+    L = L_n;
+    fb += step;
+}
+
+// k_frames with the stream loads (hash_frame_stream) and the compact image:
+// the same deal of frame groups, dynamic tail, tail pieces and exit count.
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_frames_stream(const FrameParams p)
+{
+    VCRC_STAMP(0);
+    VCRC_KARG_EARLY("s"(p.consts), "s"(p.base), "s"(p.off), "s"(p.len), "s"(p.stride), "s"(p.flen), "s"(p.last_len),
+                    "s"(p.n), "s"(p.seed0), "s"(p.seed_rest), "s"(gridDim.x));
+    constexpr int kGroups = 64 / G;
+    const int lane = threadIdx.x & 63;
+    constexpr int PF = 1;
+    constexpr bool PAY = false, C0 = false;
+    static_assert(kStreamLoads<G, PF, PAY>, "no stream-load instance of this shape");
+    const RotBases sb = rot_bases(lane);
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    RotImage im;
+    lds_rot_issue(p.consts, im);
+    PowImage pim;
+    if constexpr (PAY) lds_pow_issue(p.consts, 0, pim);
+    // Descriptors of the next frame group are fetched while this one hashes.
+    // (Loading the first group's descriptors branch-free before the blob, so
+    // the prologue overlaps the first frame loads exactly, measured slower:
+    // cfg2 -3%, 256-frame windows -9%, cfg3 -1%.)
+    uint64_t fb = wave * kGroups, f = fb + (uint64_t)(lane / G), off = 0;
+    uint32_t L = 0;
+    if (f < p.n) frame_desc(p, f, off, L);
+    // Every wave runs the first pass (lanes past the batch hash nothing): the
+    // LDS fill and the barrier sit in its hash_frame call, after the frame
+    // loads are issued. Peeled, so the LDS image's registers are dead in the
+    // loop.
+    const RotImage &cim = im;
+    const PowImage &cpim = pim;
+    group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [&cim, &cpim] {
+#ifndef VCRC_NO_LDS_FILL  // diagnostic A/B builds only (wrong CRCs): the prologue's share of small launches
+        lds_rot_write(cim);
+#endif
+        if (PAY) lds_pow_write(cpim);
+        __syncthreads();
+        VCRC_STAMP(1);
+    });
+    if (!p.qhead) {
+        while (fb < p.n) group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
+        if constexpr (kTailPieces<G, PF, PAY>) {
+            if (p.tail_n) tail_pieces<G, PF, C0>(p, lane, sb);
+        }
+        VCRC_STAMP(2);
+        return;
+    }
+    // Dynamic tail: the first static_rounds group rounds are dealt as above,
+    // the rest are pulled one group at a time from a queue, so waves that run
+    // ahead (the oldest of a SIMD issue first) take more of the end. Short
+    // groups split the queue into P interleaved partitions (group part + P * k
+    // of the dynamic range), one head word each, keyed by blockIdx % P as in the
+    // ragged kernel (every partition has a workgroup: P <= gridDim.x); long
+    // groups keep one word, which evens the end out better. The last wave out
+    // re-zeroes the heads for the next launch on this stream.
+    const uint64_t dyn = (uint64_t)p.static_rounds * nwaves * kGroups;  // first frame of the queue
+    while (fb < p.n && fb < dyn) group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
+    const uint32_t P = min(min(p.qparts, kDynParts), gridDim.x), part = blockIdx.x % P;
+    // the lane id again from mbcnt: kept live from the entry, it was the one
+    // value k_frames<16/32, 1> spilled to scratch (a scratch kernel's waves
+    // launch later)
+    // Short groups (P > 1 partitions), one group ahead: each group's dequeue is
+    // issued when the previous group starts, and its descriptors are fetched once that group's round 0 is
+    // hashed (the mid() hook, as the ragged kernel does), so a group's first
+    // loads no longer wait for an atomic and then for its descriptors: two
+    // dependent round trips per group, which short groups (1,100-B frames:
+    // five rounds) could not hide (u1100d +3.0-3.7%, profiles/r03_ab_dyn_one_ahead_gated.log).
+    // Every wave still ends on one failed dequeue, so the exit count below is
+    // unchanged.
+    const int ql = (int)__lane_id();
+    if (P == 1u) {  // long groups: dequeue at each group's start (one ahead lost cfg4 2.5%, cfg3 0.7%: a wave
+                    // then holds a reserved long group while others run dry)
+        for (;;) {
+            uint32_t k = 0;
+            if (ql == 0) k = atomicAdd(&p.qhead[0], 1u);
+            k = __builtin_amdgcn_readfirstlane(k);
+            const uint64_t gb = dyn + (uint64_t)k * kGroups;
+            if (gb >= p.n) break;
+            const uint64_t fd = gb + (uint64_t)(ql / G);
+            uint64_t od = 0;
+            uint32_t Ld = 0;
+            if (fd < p.n) frame_desc(p, fd, od, Ld);
+            hash_frame_stream<G>(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {});
+        }
+    }
+    uint32_t k = 0;
+    if (P > 1u && ql == 0) k = atomicAdd(&p.qhead[part * 16u], 1u);
+    // (Runs of 4 or 16 consecutive groups per partition, as the ragged kernel
+    // deals one-bucket batches, measured neutral here: -0.4 to +0.4%;
+    // profiles/r04_ab_dyn_tail_runs.log.)
+    uint64_t gb = P == 1u ? p.n : dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(k)) * kGroups;
+    uint64_t fd = gb + (uint64_t)(ql / G), od = 0;
+    uint32_t Ld = 0;
+    if (fd < p.n) frame_desc(p, fd, od, Ld);
+    while (gb < p.n) {
+        uint32_t kn = 0;
+        if (ql == 0) kn = atomicAdd(&p.qhead[part * 16u], 1u);
+        uint64_t gb_n = 0, fd_n = 0, od_n = 0;
+        uint32_t Ld_n = 0;
+        hash_frame_stream<G>(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {}, [&] {
             gb_n = dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(kn)) * kGroups;
             fd_n = gb_n + (uint64_t)(ql / G);
             if (fd_n < p.n) frame_desc(p, fd_n, od_n, Ld_n);

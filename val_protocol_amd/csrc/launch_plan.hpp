@@ -85,6 +85,7 @@ struct PlanKnobs {
     uint32_t ragged_min;
     uint32_t scan_front;  // 0 = by the number of streams
     uint32_t window_k0;   // file windows: log2 of the chunk bytes, 0 = automatic
+    int stream_loads = -1;  // 1 / 0: forced on / off; -1: by the rule (Planner::stream_loads)
 };
 
 using Launch = val_gpu_launch_t;
@@ -133,6 +134,25 @@ struct Planner {
         const uint32_t cap = 64u;
         while (G < cap && 2u * G <= units && (n + 64 / G - 1) / (64 / G) * 2u <= waves) G *= 2;
         return G;
+    }
+
+    // Load path of a planned k_frames launch: rounds >= 1 through nt LDS-DMA
+    // beside the compact table image (crc_kernels.hpp hash_frame_stream)
+    // instead of ordinary loads. Instances: 8 lanes per frame, the default
+    // depth, no payload states. By the rule only multi-pass launches of frames
+    // of at least 8 KiB take it: the stream is worth its longer prologue-to-
+    // first-hash path only over many rounds (cfg3: 32 rounds a frame, 32 group
+    // rounds a wave; profiles/ab_stream_loads_cfg3.jsonl), and a one-pass launch
+    // is latency-bound, not stream-bound. Forced on, every launch the instances
+    // can hash takes it (tests). 16 lanes: not measured, so not built.
+    // the frame length the rule goes by: as frames() takes it
+    uint32_t stream_len(uint32_t typical_len) const { return typical_len ? typical_len : 16384u; }
+    bool stream_loads(const Launch &l, uint32_t len) const
+    {
+        if (k.stream_loads == 0 || pay || l.lanes != 8u || l.depth != 1) return false;
+        if (l.kernel != kKernelFrames && l.kernel != kKernelFramesC0) return false;
+        if (k.stream_loads == 1) return true;
+        return l.kernel == kKernelFrames && len >= 8192u;
     }
 
     // Small batches of long frames go to k_frames_split (one workgroup per frame,

@@ -390,9 +390,13 @@ bool split_enabled()
 // loads, payload states). x: the stream scratch the launch uses (the
 // dynamic-tail queue, the tail accumulators), else null.
 template <int G>
-hipError_t launch_k_frames(const Launch &l, StreamScratch *x, hipStream_t s, const FrameParams &p)
+hipError_t launch_k_frames(const Launch &l, bool stream, StreamScratch *x, hipStream_t s, const FrameParams &p)
 {
     const dim3 grid(l.grid), b(kBlock);
+    if (stream) {  // a missing instance is an error, never a quiet change of path
+        if constexpr (kStreamLoads<G, 1, false>) return launch_tracked(x, k_frames_stream<G>, grid, b, s, p);
+        else return hipErrorInvalidValue;
+    }
     if (p.out_pay) return launch_tracked(x, k_frames<G, 1, true>, grid, b, s, p);
     if (l.kernel == kKernelFramesC0) return launch_tracked(x, k_frames<G, 1, false, true>, grid, b, s, p);
     if constexpr (G == 2 || G == 4) {
@@ -412,6 +416,17 @@ hipError_t launch_k_frames(const Launch &l, StreamScratch *x, hipStream_t s, con
 // or val_gpu_set_tail_pieces(0) keeps the second launch (A/B).
 std::atomic<int> g_tail_pieces{-1};  // -1: VAL_GPU_TAIL_PIECES (unset = on); 0 / 1: val_gpu_set_tail_pieces
 std::atomic<uint64_t> g_tail_piece_launches{0};
+// Stream loads (launch_plan.hpp Planner::stream_loads): VAL_GPU_STREAM_LOADS=0 / 1
+// or val_gpu_set_stream_loads() force the path off / on; unset: the rule.
+std::atomic<int> g_stream_loads{-1};
+std::atomic<uint64_t> g_stream_load_launches{0};
+int stream_loads_mode()
+{
+    const int v = g_stream_loads.load(std::memory_order_relaxed);
+    if (v >= 0) return v;
+    static const int env = getenv("VAL_GPU_STREAM_LOADS") ? (atoi(getenv("VAL_GPU_STREAM_LOADS")) != 0 ? 1 : 0) : -1;
+    return env;
+}
 bool tail_pieces_enabled()
 {
     const int v = g_tail_pieces.load(std::memory_order_relaxed);
@@ -430,7 +445,7 @@ val_status_t launch_split(const Ctx &c, FrameParams &p, const Launch &l, hipStre
 
 // One planned k_frames launch: the tail accumulators and the queue the plan
 // asks for, then the kernel.
-val_status_t launch_uniform_one(Ctx &c, FrameParams &p, const Launch &l, hipStream_t s)
+val_status_t launch_uniform_one(Ctx &c, FrameParams &p, const Launch &l, bool stream, hipStream_t s)
 {
     p.consts = c.d_consts;
     p.qhead = nullptr;
@@ -462,7 +477,7 @@ val_status_t launch_uniform_one(Ctx &c, FrameParams &p, const Launch &l, hipStre
         p.static_rounds = l.static_rounds;
     }
     return launch_at_lanes(l.lanes, "k_frames launch", [&](auto G) {
-        const hipError_t e = launch_k_frames<decltype(G)::value>(l, used, s, p);
+        const hipError_t e = launch_k_frames<decltype(G)::value>(l, stream, used, s, p);
         if (p.tail_n && e == hipSuccess) used->tail.counts_zero = true;
         return e;
     });
@@ -663,7 +678,7 @@ PlanKnobs plan_knobs()
 {
     return PlanKnobs{forced_lanes(), forced_prefetch(), dyn_tail_enabled(), split_enabled(), tail_pieces_enabled(),
                      ragged_min_frames(), g_scan_front.load(std::memory_order_relaxed),
-                     g_window_k0.load(std::memory_order_relaxed)};
+                     g_window_k0.load(std::memory_order_relaxed), stream_loads_mode()};
 }
 
 // Frames [l.first, l.first + l.count) of batch p as a batch of their own, with
@@ -698,8 +713,8 @@ FrameParams slice_frames(const FrameParams &p, const Launch &l)
 // Plans the batch (launch_plan.hpp) and executes the plan.
 val_status_t launch_frames(Ctx &c, FrameParams &p, uint32_t typical_len, hipStream_t s)
 {
-    const LaunchPlan plan =
-        plan_frames((uint32_t)c.cus, p.n, typical_len, p.off != nullptr, p.flen, p.last_len, p.out_pay != nullptr, plan_knobs());
+    const Planner planner{(uint32_t)c.cus, p.off != nullptr, p.out_pay != nullptr, p.flen, p.last_len, plan_knobs()};
+    const LaunchPlan plan = planner.frames(p.n, typical_len);
     for (uint32_t i = 0; i < plan.count; i++) {
         const Launch &l = plan.launch[i];
         val_status_t st = VAL_OK;
@@ -707,7 +722,9 @@ val_status_t launch_frames(Ctx &c, FrameParams &p, uint32_t typical_len, hipStre
             st = launch_ragged(c, p, l, s);
         } else {
             FrameParams q = slice_frames(p, l);
-            st = l.kernel == kKernelSplit ? launch_split(c, q, l, s) : launch_uniform_one(c, q, l, s);
+            const bool stream = l.kernel != kKernelSplit && planner.stream_loads(l, planner.stream_len(typical_len));
+            st = l.kernel == kKernelSplit ? launch_split(c, q, l, s) : launch_uniform_one(c, q, l, stream, s);
+            if (stream && st == VAL_OK) g_stream_load_launches.fetch_add(1, std::memory_order_relaxed);
         }
         if (st != VAL_OK) return st;
         if (l.tail_n) g_tail_piece_launches.fetch_add(1, std::memory_order_relaxed);
@@ -2040,6 +2057,10 @@ void val_gpu_set_tail_pieces(int enable) { g_tail_pieces.store(enable < 0 ? -1 :
 
 uint64_t val_gpu_tail_piece_launches(void) { return g_tail_piece_launches.load(std::memory_order_relaxed); }
 
+void val_gpu_set_stream_loads(int enable) { g_stream_loads.store(enable < 0 ? -1 : (enable ? 1 : 0)); }
+
+uint64_t val_gpu_stream_load_launches(void) { return g_stream_load_launches.load(std::memory_order_relaxed); }
+
 uint64_t val_gpu_host_multi_min_bytes_ex(int devices, int pinned, uint64_t mean_len)
 {
     return host_multi_min_bytes(devices, mean_len, pinned != 0);
@@ -2149,6 +2170,19 @@ uint32_t val_gpu_plan_frames(uint32_t cus, uint32_t n, int descriptors, uint32_t
     const LaunchPlan plan =
         plan_frames(cus, n, typical_len, descriptors != 0, flen, last_len, want_payload != 0, plan_knobs());
     for (uint32_t i = 0; out_plan && i < plan.count; i++) out_plan[i] = plan.launch[i];
+    return plan.count;
+}
+
+uint32_t val_gpu_plan_stream_loads(uint32_t cus, uint32_t n, int descriptors, uint32_t typical_len, uint32_t flen,
+                                   uint32_t last_len, int want_payload, int out_stream[2])
+{
+    const Planner planner{cus, descriptors != 0, want_payload != 0, flen, last_len, plan_knobs()};
+    const LaunchPlan plan = planner.frames(n, typical_len);
+    for (uint32_t i = 0; out_stream && i < plan.count; i++) {
+        const Launch &l = plan.launch[i];
+        out_stream[i] = (l.kernel == kKernelFrames || l.kernel == kKernelFramesC0) &&
+                        planner.stream_loads(l, planner.stream_len(typical_len));
+    }
     return plan.count;
 }
 

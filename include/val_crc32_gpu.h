@@ -418,6 +418,109 @@ val_status_t val_frame_fill_files_dev(const uint8_t *d_payload, const uint64_t *
                                       uint64_t *d_frame_off, uint32_t *d_crc_len, uint32_t *d_crc, uint32_t *d_hdr,
                                       void *d_work, uint64_t work_bytes, void *stream);
 
+/* The receiver's answers to a delivered window, on the device: the DATA_ACK /
+ * DATA_NAK frames the reference's receive loop sends for the DATA frames of a
+ * window (src/val_receiver.c:871-1000, encoded as src/val_core.c:775-811 with
+ * the trailer of :828-834), for n_files transfers in one asynchronous call.
+ * It runs on the stream right after val_frame_unpack_files_dev, over the same
+ * window and that call's results. Async on `stream`; all pointers are device
+ * pointers; nothing is synchronised and no library scratch is kept.
+ * Inputs: the frame descriptors as there (d_base, d_off, d_len, stride, flen,
+ * n, n_files, d_first, clamped the same way, so a frame that no file owns gets
+ * no response); that call's d_ok[] and d_accept[] (both required) and its
+ * d_written[], the positions AFTER delivery; d_total[s], the incoming file's
+ * size; ack_stride (the handshake's ack_stride_packets) and d_since[s], the
+ * frames accepted since the last stride ACK (in/out; may be NULL when
+ * ack_stride == 0, which neither reads nor writes it).
+ * Per file s the call writes the wire bytes of exactly the responses
+ * val_frame_respond_window (val_wire.h) lists for that file's frames, each as
+ * val_frame_put_response lays it out, trailer included, back to back from
+ * d_out + d_resp_off[s]; d_resp_len[s] = the bytes used, d_nresp[s] = the
+ * frames written (both set; 0 for a file without frames); d_ndropped[s]
+ * (nullable) is INCREMENTED by the responses that did not fit.
+ * Capacity: with pos_r the sum of the wire sizes of the file's earlier
+ * responses, response r is written iff pos_r + size_r <= d_resp_cap[s]. That
+ * keeps a prefix; every later response is dropped and counted.
+ * val_frame_respond_bytes_max(frames) = 40 * frames bounds a file's stream (a
+ * gap answers with a 24-byte NAK and an ACK of up to 16 bytes).
+ * Only the wire bytes of kept responses are written; every other byte of d_out
+ * keeps its value. Of each frame only the header dwords and, for an explicit
+ * DATA frame, its offset dwords are read. d_out, d_resp_off and d_resp_len
+ * feed val_frame_scan_streams_dev unchanged.
+ * No position before the unpack call exists in HBM: the position in front of
+ * frame i is d_written[s] minus the payload bytes of the file's accepted
+ * frames at indices >= i. A DATA frame with d_accept[i] == 0, d_ok[i] != 0 and
+ * an offset (explicit or implied) equal to that position was refused by
+ * capacity alone and is silent.
+ * It is a short pipeline on the stream: the header
+ * facts grid-wide, the rule as segmented scans (workgroups take whole files in
+ * turn, 1,024 or 256 frames per chunk), and the response frames grid-wide, each
+ * trailer computed where its frame is written.
+ * d_work: val_frame_respond_work_bytes(n) bytes, 8-byte aligned (the header
+ * facts and every frame's planned responses); its contents after the call are
+ * unspecified. Overlapping segments are the caller's error: a frame owned
+ * twice is answered in either file's stream, never outside that stream's
+ * capacity. Response streams must not overlap each other.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when d_off and d_len are not both set or both NULL, d_work is NULL or
+ * misaligned, work_bytes is below val_frame_respond_work_bytes(n), and, with
+ * n > 0 and n_files > 0, when d_first, d_ok, d_accept, d_written, d_total,
+ * d_out, d_resp_off, d_resp_cap, d_resp_len, d_nresp or d_base is NULL, or
+ * d_since is NULL with ack_stride > 0. Otherwise n == 0 or n_files == 0
+ * returns VAL_OK, launches nothing and changes nothing (d_resp_len included).
+ * The call runs on the stream's device (else the device d_written lives on). */
+uint64_t val_frame_respond_bytes_max(uint64_t frames);
+uint64_t val_frame_respond_work_bytes(uint32_t n);
+val_status_t val_frame_respond_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                         uint64_t stride, uint32_t flen, uint32_t n, uint32_t n_files,
+                                         const uint32_t *d_first, const uint8_t *d_ok, const uint8_t *d_accept,
+                                         const uint64_t *d_written, const uint64_t *d_total, uint32_t ack_stride,
+                                         uint32_t *d_since, uint8_t *d_out, const uint64_t *d_resp_off,
+                                         const uint64_t *d_resp_cap, uint64_t *d_resp_len, uint32_t *d_nresp,
+                                         uint32_t *d_ndropped, void *d_work, uint64_t work_bytes, void *stream);
+
+/* The sender's handling of the answers, on the device: a window of received
+ * DATA_ACK / DATA_NAK frames of n_files transfers (what
+ * val_frame_scan_streams_dev described) moves every transfer's d_last_acked[s]
+ * and d_next[s] as wait_for_window_ack does (reference
+ * src/val_sender.c:404-555), in one asynchronous call. Async on `stream`; all
+ * pointers are device pointers; nothing is synchronised.
+ * Frames are described as for val_frame_unpack_files_dev (d_base, d_off,
+ * d_len, stride, flen, n, len_hint, n_files, d_first, clamped the same way).
+ * The pipeline is the verify launches of val_crc32_verify_frames_dev (d_ok[i]
+ * nullable, *d_nbad nullable and INCREMENTED, as in the unpack call), then one
+ * apply launch: per transfer s, d_last_acked[s] and d_next[s] become exactly
+ * what val_frame_apply_acks (val_wire.h) leaves for that transfer's frames,
+ * with val_frame_ack_offsets' kinds and offsets, the trailer verdicts as ok[]
+ * and file_size = d_file_size[s]; d_nretrans[s] and d_file_nbad[s] (arrays
+ * nullable; zero them first) are INCREMENTED by the rule's retransmits and CRC
+ * errors. The rule reduces to a maximum and an "any restart" per transfer, so
+ * the launch is a reduction in the respond call's per-file layout. A transfer
+ * without frames keeps its entries; a frame that no transfer owns is verified
+ * and otherwise ignored. d_next and d_last_acked then feed
+ * val_frame_fill_files_dev unchanged. Timeouts stay the host's: a go-back-N
+ * restart after silence is d_next[s] = d_last_acked[s].
+ * Of each frame the verify stage reads the CRC input and the trailer; the
+ * apply launch reads the two header dwords and the dword behind them when it
+ * belongs to the CRC input.
+ * d_work: val_frame_apply_acks_work_bytes(n) bytes, 8-byte aligned (the
+ * verdicts when d_ok is NULL); no library scratch beyond what the verify stage
+ * keeps per stream.
+ * Returns VAL_ERR_INVALID_ARG before any launch (val_gpu_last_error says
+ * which) when d_off and d_len are not both set or both NULL, d_work is NULL or
+ * misaligned, work_bytes is below val_frame_apply_acks_work_bytes(n), and,
+ * with n > 0 and n_files > 0, when d_first, d_file_size, d_last_acked, d_next
+ * or d_base is NULL. Otherwise n == 0 or n_files == 0 returns VAL_OK, launches
+ * nothing and changes nothing. The call runs on the stream's device (else the
+ * device d_last_acked lives on). */
+uint64_t val_frame_apply_acks_work_bytes(uint32_t n);
+val_status_t val_frame_apply_acks_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                            uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint,
+                                            uint32_t n_files, const uint32_t *d_first, const uint64_t *d_file_size,
+                                            uint64_t *d_last_acked, uint64_t *d_next, uint32_t *d_nretrans,
+                                            uint32_t *d_file_nbad, uint8_t *d_ok, uint32_t *d_nbad, void *d_work,
+                                            uint64_t work_bytes, void *stream);
+
 /* CRC-32 of one byte window of each of n_files GPU-resident files, in one
  * device call: the many-files form of val_crc32_region_dev, for callers whose
  * file sizes and windows exist only in HBM (a receiver that has just delivered
@@ -731,7 +834,11 @@ enum {
     VAL_GPU_KERNEL_FILL_DESC = 13,
     /* the file-window calls' kernels (val_gpu_plan_file_windows) */
     VAL_GPU_KERNEL_WINDOWS_COUNT = 14,
-    VAL_GPU_KERNEL_WINDOWS_HASH = 15
+    VAL_GPU_KERNEL_WINDOWS_HASH = 15,
+    /* the ACK calls' kernels (val_gpu_plan_ack_calls) */
+    VAL_GPU_KERNEL_ACK_RESPOND_FILES = 16,
+    VAL_GPU_KERNEL_ACK_EMIT = 17,
+    VAL_GPU_KERNEL_ACK_APPLY_FILES = 18
 };
 typedef struct val_gpu_launch {
     uint32_t kernel;        /* VAL_GPU_KERNEL_* */
@@ -776,6 +883,17 @@ uint32_t val_gpu_plan_window(uint32_t call, uint32_t cus, uint32_t n, uint32_t g
  * 0 for n_files == 0 and for a call that is refused (max_len above 2^32, or
  * the chunk product overflowing 32 bits). */
 uint32_t val_gpu_plan_file_windows(uint32_t cus, uint32_t n_files, uint64_t max_len, val_gpu_launch_t out[3]);
+/* The launches val_frame_respond_files_dev (VAL_GPU_ACK_RESPOND: the header
+ * facts, the rule, the response frames) and val_frame_apply_acks_files_dev
+ * (VAL_GPU_ACK_APPLY: one launch after its verify launches, which are
+ * val_gpu_plan_frames) would make for n frames of n_files files on a device of
+ * `cus` compute units, in order; kernel, grid and count (the frames or files
+ * the grid covers) are set, and on the respond call's rule launch lanes, the
+ * threads of a workgroup (256 when the files own 256 frames or fewer on
+ * average, else 1,024; speed only). Needs no device. Returns the number of launches
+ * written: 0 for an unknown call, n == 0 or n_files == 0. */
+enum { VAL_GPU_ACK_RESPOND = 0, VAL_GPU_ACK_APPLY = 1 };
+uint32_t val_gpu_plan_ack_calls(uint32_t call, uint32_t cus, uint32_t n, uint32_t n_files, val_gpu_launch_t out[3]);
 /* Chunk bytes 2^k0 of the file-window calls: 12..16 force them, 0 restores
  * the automatic choice (the smallest of 4 .. 64 KiB at which n_files windows
  * of max_len bytes are at most one chunk per wave of the device); any other

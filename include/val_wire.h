@@ -279,6 +279,93 @@ int val_resume_request_window(uint64_t resume_offset, uint64_t verify_len, uint6
 val_status_t val_resume_verdict(int window_ok, uint32_t local_crc, uint32_t sender_crc, int mismatch_skip,
                                 uint64_t rec_resume_off, uint64_t file_size, uint64_t *resume_off_out);
 
+/*
+ * DATA_ACK / DATA_NAK: the receiver's answers to DATA frames and the sender's
+ * handling of them (reference src/val_receiver.c:871-1000, src/val_core.c:
+ * 775-811,828-834,995-1009, src/val_sender.c:404-555), host only. The device
+ * calls val_frame_respond_files_dev and val_frame_apply_acks_files_dev
+ * (val_crc32_gpu.h) apply the same rules per file.
+ *
+ * val_frame_put_response: one response frame with its trailer (the library's
+ * CPU engine hashes it) into out[]; returns its wire size, 0 for another kind
+ * or a NULL out.
+ *   VAL_PKT_DATA_ACK (6): flags 0, type_data = low 32 bits of `offset`; no
+ *     content (12 wire bytes) when offset < 2^32, else the LE32 high half
+ *     (16 wire bytes). `reason` is unused.
+ *   VAL_PKT_DATA_NAK (13): flags 0, content_len 12, type_data = low 32 bits;
+ *     content LE32 high, LE32 reason, LE32 0 (24 wire bytes).
+ * out needs VAL_WIRE_RESPONSE_MAX bytes.
+ */
+#define VAL_WIRE_RESPONSE_MAX 24u
+#define VAL_NAK_REASON_GAP 1u
+uint32_t val_frame_put_response(uint8_t kind, uint64_t offset, uint32_t reason, uint8_t *out);
+
+/*
+ * The inverse over scanned frames (val_frame_scan's frame_off / crc_len):
+ * kind[i] = 6 or 13 when byte 0 says so and crc_len[i] >= 8, else 0;
+ * ack_off[i] = type_data | (crc_len[i] >= 12 ? LE32 at +8 : 0) << 32 for
+ * those, 0 for kind 0. Either output may be NULL.
+ */
+void val_frame_ack_offsets(const uint8_t *stream, const uint64_t *frame_off, const uint32_t *crc_len, uint32_t n,
+                           uint8_t *kind, uint64_t *ack_off);
+
+/*
+ * The receiver's answer to one file's window: val_frame_accept's inputs
+ * (file_off[], pay_len[], ok[] (NULL = all good), n, file_cap, *written), plus
+ * `total`, the incoming file's size from SEND_META, ack_stride (the
+ * handshake's ack_stride_packets) and *since, the frames accepted since the
+ * last stride ACK (in/out). The responses come in frame order:
+ * resp_frame[r] is the index of the frame that caused response r,
+ * resp_kind[r] 6 or 13, resp_off[r] its offset (room for 2n entries each, each
+ * nullable), *n_resp their number (nullable, set).
+ * With W = *written, frame after frame; frames with ok[i] == 0 and non-DATA
+ * frames are skipped. eff = W for an implied offset, else file_off[i].
+ *   eff == W: a frame that val_frame_accept's capacity test refuses gets no
+ *     response. Otherwise W += pay_len[i]; if W >= total: ACK(W), since = 0;
+ *     else since++ (saturating), and when ack_stride >= 1 and
+ *     since >= ack_stride: ACK(W), since = 0.
+ *   eff <  W: ACK(W): a duplicate is reaffirmed; since is left alone.
+ *   eff >  W: NAK(W), then ACK(W).
+ * ack_stride == 0 is the handshake's "one ACK per window": since is neither
+ * read nor written (it may be NULL); an accepted frame emits ACK(W) only when
+ * W >= total, and the last accepted frame of the call also emits ACK(W) if it
+ * emitted nothing.
+ * The accepted frames and the final *written are val_frame_accept's for the
+ * same inputs. All arithmetic is 64-bit and never wraps.
+ * Two differences from the reference: a frame refused by capacity alone is
+ * silent here, where the reference aborts the transfer on a failed fwrite; and
+ * stride values other than 1 follow the reference's formula
+ * (src/val_receiver.c:975-1000), which the reference itself only ever runs at
+ * 1.
+ */
+void val_frame_respond_window(const uint64_t *file_off, const uint32_t *pay_len, const uint8_t *ok, uint32_t n,
+                              uint64_t file_cap, uint64_t total, uint32_t ack_stride, uint64_t *written,
+                              uint32_t *since, uint32_t *resp_frame, uint8_t *resp_kind, uint64_t *resp_off,
+                              uint32_t *n_resp);
+
+/*
+ * The sender's handling of one transfer's response window
+ * (wait_for_window_ack, reference src/val_sender.c:404-555): kind[] and
+ * ack_off[] from val_frame_ack_offsets, ok[] the trailer verdicts (NULL = all
+ * good). With la = *last_acked and nx = *next, frame after frame:
+ *   ok[i] == 0: nx = la; a retransmit and a CRC error are counted (the
+ *     restart of :542-553).
+ *   kind 6:  if la < off && off <= file_size then la = off; any other ACK is
+ *     stale and ignored.
+ *   kind 13: the same advance, then nx = la; a retransmit is counted
+ *     (:432-453, :317-346).
+ *   kind 0:  ignored.
+ * After the last frame, nx < la becomes nx = la. *n_retrans and *n_crc
+ * (nullable) are set, not incremented. All arithmetic is 64-bit and never
+ * wraps.
+ * One addition to the reference: it does not test an ACK's offset against
+ * file_size; this rule does, which keeps last_acked <= file_size, as
+ * val_frame_fill_window relies on.
+ */
+void val_frame_apply_acks(const uint8_t *kind, const uint64_t *ack_off, const uint8_t *ok, uint32_t n,
+                          uint64_t file_size, uint64_t *last_acked, uint64_t *next, uint32_t *n_retrans,
+                          uint32_t *n_crc);
+
 #ifdef __cplusplus
 }
 #endif

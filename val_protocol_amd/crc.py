@@ -75,6 +75,9 @@ EXPORTS = (
     "val_file_windows_work_bytes", "val_crc32_file_windows_dev", "val_resume_tail_files_dev",
     "val_resume_request_files_dev", "val_resume_check_files_dev", "val_gpu_plan_file_windows",
     "val_gpu_set_file_window_chunk",
+    "val_frame_put_response", "val_frame_ack_offsets", "val_frame_respond_window", "val_frame_apply_acks",
+    "val_frame_respond_bytes_max", "val_frame_respond_work_bytes", "val_frame_respond_files_dev",
+    "val_frame_apply_acks_work_bytes", "val_frame_apply_acks_files_dev", "val_gpu_plan_ack_calls",
 )
 
 # Where the calling thread's last scalar-hook call was answered (val_gpu_last_hook_path).
@@ -92,6 +95,8 @@ KERNEL_RAGGED, KERNEL_SPLIT, KERNEL_FRAMES, KERNEL_FRAMES_C0 = 0, 1, 2, 3
 (KERNEL_PACK, KERNEL_UNPACK_PARSE, KERNEL_UNPACK_ORDER, KERNEL_UNPACK_ORDER_FILES, KERNEL_UNPACK, KERNEL_SCAN_STREAMS,
  KERNEL_SCAN_FIRST, KERNEL_SCAN_COMPACT, KERNEL_FILL_COUNT, KERNEL_FILL_DESC) = range(4, 14)
 KERNEL_WINDOWS_COUNT, KERNEL_WINDOWS_HASH = 14, 15  # val_gpu_plan_file_windows
+KERNEL_ACK_RESPOND_FILES, KERNEL_ACK_EMIT, KERNEL_ACK_APPLY_FILES = 16, 17, 18  # val_gpu_plan_ack_calls
+ACK_RESPOND, ACK_APPLY = 0, 1
 # val_gpu_plan_window: the window calls
 WINDOW_PACK, WINDOW_UNPACK, WINDOW_UNPACK_FILES, WINDOW_SCAN, WINDOW_FILL = range(5)
 
@@ -215,6 +220,20 @@ def _declare(lib: ctypes.CDLL, strict: bool = True) -> None:
        ctypes.POINTER(u32))
     fn("val_gpu_plan_frames", u32, u32, u32, ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(Launch))
     fn("val_gpu_plan_window", u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(Launch))
+    fn("val_frame_put_response", u32, ctypes.c_uint8, u64, u32, _vp)
+    fn("val_frame_ack_offsets", None, _vp, _vp, _vp, u32, _vp, _vp)
+    fn("val_frame_respond_window", None, _vp, _vp, _vp, u32, u64, u64, u32, ctypes.POINTER(u64), ctypes.POINTER(u32),
+       _vp, _vp, _vp, ctypes.POINTER(u32))
+    fn("val_frame_apply_acks", None, _vp, _vp, _vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+       ctypes.POINTER(u32), ctypes.POINTER(u32))
+    fn("val_frame_respond_bytes_max", u64, u64)
+    fn("val_frame_respond_work_bytes", u64, u32)
+    fn("val_frame_respond_files_dev", i32, _vp, _vp, _vp, u64, u32, u32, u32, _vp, _vp, _vp, _vp, _vp, u32, _vp, _vp,
+       _vp, _vp, _vp, _vp, _vp, _vp, u64, _vp)
+    fn("val_frame_apply_acks_work_bytes", u64, u32)
+    fn("val_frame_apply_acks_files_dev", i32, _vp, _vp, _vp, u64, u32, u32, u32, u32, _vp, _vp, _vp, _vp, _vp, _vp,
+       _vp, _vp, _vp, u64, _vp)
+    fn("val_gpu_plan_ack_calls", u32, u32, u32, u32, u32, ctypes.POINTER(Launch))
     fn("val_resume_tail_window", ctypes.c_int, u64, u64, u64, u64, ctypes.c_int, ctypes.POINTER(u64),
        ctypes.POINTER(u64))
     fn("val_resume_request_window", ctypes.c_int, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u32))
@@ -478,6 +497,16 @@ def plan_window(call: int, cus: int, n: int, *, groups: int = 0, max_frames: int
     the files of WINDOW_UNPACK_FILES; len_hint: the fill's mtu. Needs no GPU."""
     out = (Launch * 4)()
     k = lib().val_gpu_plan_window(call, cus, n, groups, max_frames, len_hint, out)
+    return [out[i] for i in range(k)]
+
+
+def plan_ack_calls(call: int, cus: int, n: int, n_files: int) -> list:
+    """The launches (Launch, at most three: kernel, grid, count) of
+    wire.respond_files_dev (ACK_RESPOND) or, after its verify launches, of
+    wire.apply_acks_files_dev (ACK_APPLY) for n frames of n_files files. Needs
+    no GPU."""
+    out = (Launch * 3)()
+    k = lib().val_gpu_plan_ack_calls(call, cus, n, n_files, out)
     return [out[i] for i in range(k)]
 
 

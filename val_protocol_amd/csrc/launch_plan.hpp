@@ -2,9 +2,9 @@
 // with how many lanes, which round loop and which grid, and whether it takes
 // the dynamic tail, the in-launch tail pieces or the split kernel
 // (plan_frames()); and the lanes and grids of the window calls' launches: the
-// framer, both unpack calls, the scan, the fill and the file windows
-// (plan_pack(), plan_unpack(), plan_scan(), plan_fill(),
-// plan_file_windows()). They map plain numbers to
+// framer, both unpack calls, the scan, the fill, the file windows and the
+// ACK calls (plan_pack(), plan_unpack(), plan_scan(), plan_fill(),
+// plan_file_windows(), plan_ack()). They map plain numbers to
 // launches and call no HIP API; val_crc32_hip.hip fills in the kernels'
 // params, executes a plan and decides nothing. tests/test_launch_plan.py pins
 // the plans of a table of shapes through val_gpu_plan_frames() and
@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "ack_kernel.hpp"
 #include "crc_kernels.hpp"
 #include "fill_kernel.hpp"
 #include "pack_kernel.hpp"
@@ -501,6 +502,32 @@ inline WindowPlan plan_file_windows(uint32_t cus32, uint32_t n_files, uint64_t m
     const uint64_t chunks = window_chunks(n_files, max_len, k0);
     pl.add(VAL_GPU_KERNEL_WINDOWS_HASH, std::min<uint64_t>((chunks + kWavesPerBlock - 1) / kWavesPerBlock, cus), chunks);
     pl.launch[2].k0 = k0;
+    return pl;
+}
+
+// The ACK calls (ack_kernel.hpp), after their verify launches if any.
+// Respond: the header facts grid-wide (k_unpack_parse), the rule in
+// k_unpack_order_files' layout (a workgroup per file up to one per CU, each
+// taking whole files in turn: the scans are sequential only within a file;
+// workgroups of 256 threads, up to eight per CU, when the files are small),
+// then the response frames grid-wide, one frame per thread. Apply: one launch
+// in the same per-file layout.
+inline WindowPlan plan_ack(uint32_t call, uint32_t cus, uint32_t n, uint32_t n_files)
+{
+    WindowPlan pl;
+    if (n == 0 || n_files == 0) return pl;
+    const uint64_t files_grid = std::min(n_files, std::max(cus, 1u));
+    if (call == VAL_GPU_ACK_RESPOND) {
+        pl.add(VAL_GPU_KERNEL_UNPACK_PARSE, ((uint64_t)n + 255u) / 256u, n);
+        // lanes = the workgroup's threads: small files run eight workgroups of 256 per CU side by side
+        if (n / n_files <= (uint32_t)kAckSmallFrames)
+            pl.add(VAL_GPU_KERNEL_ACK_RESPOND_FILES,
+                   std::min<uint64_t>(n_files, (uint64_t)std::max(cus, 1u) * kAckSmallPerCU), n_files, kAckSmallBlock);
+        else pl.add(VAL_GPU_KERNEL_ACK_RESPOND_FILES, files_grid, n_files, kAckBlock);
+        pl.add(VAL_GPU_KERNEL_ACK_EMIT, ((uint64_t)n + kAckEmitBlock - 1) / kAckEmitBlock, n);
+    } else if (call == VAL_GPU_ACK_APPLY) {
+        pl.add(VAL_GPU_KERNEL_ACK_APPLY_FILES, files_grid, n_files);
+    }
     return pl;
 }
 

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "ack_kernel.hpp"
 #include "cpu_crc32.h"
 #include "crc_kernels.hpp"
 #include "fill_kernel.hpp"
@@ -1819,6 +1820,27 @@ val_status_t unpack_launch(Ctx &c, UnpackParams &u, bool files, const uint8_t *d
     });
 }
 
+// Workspace of val_frame_respond_files_dev for n frames: the parsed offsets,
+// the offsets the responses carry and their places (u64), the payload lengths
+// (u32).
+struct RespondWork {
+    uint64_t *foff, *woff, *wmeta;
+    uint32_t *plen;
+    uint64_t bytes;
+    RespondWork(void *d_work, uint32_t n)
+    {
+        Carve w{(uintptr_t)d_work};
+        foff = w.take<uint64_t>(n);
+        woff = w.take<uint64_t>(n);
+        wmeta = w.take<uint64_t>(n);
+        plen = w.take<uint32_t>(n);
+        bytes = (w.used + 15u) & ~(uint64_t)15;
+    }
+};
+
+// Workspace of val_frame_apply_acks_files_dev: the verdicts (u8).
+uint64_t apply_acks_work(uint32_t n) { return ((uint64_t)n + 15u) & ~(uint64_t)15; }
+
 // Workspace of val_frame_scan_streams_dev: every stream's slot of max_frames
 // descriptors (u64 offset, u32 length) and the streams' counts (u32). A
 // product beyond 32 bits, which the call refuses, asks for more than any
@@ -2414,6 +2436,144 @@ val_status_t val_frame_unpack_files_dev(const uint8_t *d_base, const uint64_t *d
     u.file_nbad = d_file_nbad;
     return unpack_launch(*c, u, true, d_base, d_off, d_len, stride, flen, n, len_hint, d_ok, d_nbad, d_accept, d_work,
                          pick_stream(stream));
+}
+
+uint64_t val_frame_respond_bytes_max(uint64_t frames)
+{
+    return frames > UINT64_MAX / 40u ? UINT64_MAX : frames * 40u;
+}
+
+uint64_t val_frame_respond_work_bytes(uint32_t n) { return RespondWork(nullptr, n).bytes; }
+
+val_status_t val_frame_respond_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                         uint64_t stride, uint32_t flen, uint32_t n, uint32_t n_files,
+                                         const uint32_t *d_first, const uint8_t *d_ok, const uint8_t *d_accept,
+                                         const uint64_t *d_written, const uint64_t *d_total, uint32_t ack_stride,
+                                         uint32_t *d_since, uint8_t *d_out, const uint64_t *d_resp_off,
+                                         const uint64_t *d_resp_cap, uint64_t *d_resp_len, uint32_t *d_nresp,
+                                         uint32_t *d_ndropped, void *d_work, uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    val_status_t st = check_off_len(d_off, d_len);
+    if (st != VAL_OK) return st;
+    st = check_work(d_work, work_bytes, val_frame_respond_work_bytes(n),
+                    "work_bytes below val_frame_respond_work_bytes(n)");
+    if (st != VAL_OK) return st;
+    if (n == 0 || n_files == 0) return VAL_OK;
+    if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
+    if (!d_ok || !d_accept) return fail(VAL_ERR_INVALID_ARG, "ok or accept is NULL");
+    if (!d_written) return fail(VAL_ERR_INVALID_ARG, "written is NULL");
+    if (!d_total) return fail(VAL_ERR_INVALID_ARG, "total is NULL");
+    if (ack_stride && !d_since) return fail(VAL_ERR_INVALID_ARG, "since is NULL with ack_stride > 0");
+    if (!d_out || !d_resp_off || !d_resp_cap) return fail(VAL_ERR_INVALID_ARG, "out, resp_off or resp_cap is NULL");
+    if (!d_resp_len || !d_nresp) return fail(VAL_ERR_INVALID_ARG, "resp_len or nresp is NULL");
+    if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    if ((st = cur_dev(stream, d_written, &c)) != VAL_OK) return st;
+    const hipStream_t s = pick_stream(stream);
+    const RespondWork w(d_work, n);
+    const WindowPlan plan = plan_ack(VAL_GPU_ACK_RESPOND, (uint32_t)c->cus, n, n_files);
+    // a frame that no file owns is visited by no respond workgroup: it starts with no response
+    VCRC_HIP(hipMemsetAsync(w.wmeta, 0, (size_t)n * 8u, s), "memset(respond work)");
+    UnpackParams u{};
+    u.base = d_base;
+    u.off = d_off;
+    u.len = d_len;
+    u.stride = stride;
+    u.flen = flen;
+    u.n = n;
+    u.ok = d_ok;
+    u.foff = w.foff;
+    u.plen = w.plen;
+    hipLaunchKernelGGL(k_unpack_parse<false>, dim3(plan.launch[0].grid), dim3(256), 0, s, u);
+    VCRC_HIP(hipGetLastError(), "k_unpack_parse launch");
+    AckRespondParams p{};
+    p.n = n;
+    p.n_files = n_files;
+    p.first = d_first;
+    p.accept = d_accept;
+    p.foff = w.foff;
+    p.plen = w.plen;
+    p.written = d_written;
+    p.total = d_total;
+    p.ack_stride = ack_stride;
+    p.since = d_since;
+    p.out = d_out;
+    p.resp_off = d_resp_off;
+    p.resp_cap = d_resp_cap;
+    p.resp_len = d_resp_len;
+    p.nresp = d_nresp;
+    p.ndropped = d_ndropped;
+    p.woff = w.woff;
+    p.wmeta = w.wmeta;
+    if (plan.launch[1].lanes == (uint32_t)kAckSmallBlock)
+        hipLaunchKernelGGL(k_ack_respond_files<kAckSmallBlock>, dim3(plan.launch[1].grid), dim3(kAckSmallBlock), 0, s, p);
+    else hipLaunchKernelGGL(k_ack_respond_files<kAckBlock>, dim3(plan.launch[1].grid), dim3(kAckBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_ack_respond_files launch");
+    hipLaunchKernelGGL(k_ack_emit, dim3(plan.launch[2].grid), dim3(kAckEmitBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_ack_emit launch");
+    return VAL_OK;
+}
+
+uint64_t val_frame_apply_acks_work_bytes(uint32_t n) { return apply_acks_work(n); }
+
+val_status_t val_frame_apply_acks_files_dev(const uint8_t *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                            uint64_t stride, uint32_t flen, uint32_t n, uint32_t len_hint,
+                                            uint32_t n_files, const uint32_t *d_first, const uint64_t *d_file_size,
+                                            uint64_t *d_last_acked, uint64_t *d_next, uint32_t *d_nretrans,
+                                            uint32_t *d_file_nbad, uint8_t *d_ok, uint32_t *d_nbad, void *d_work,
+                                            uint64_t work_bytes, void *stream)
+{
+    t_err.clear();
+    val_status_t st = check_off_len(d_off, d_len);
+    if (st != VAL_OK) return st;
+    st = check_work(d_work, work_bytes, val_frame_apply_acks_work_bytes(n),
+                    "work_bytes below val_frame_apply_acks_work_bytes(n)");
+    if (st != VAL_OK) return st;
+    if (n == 0 || n_files == 0) return VAL_OK;
+    if (!d_first) return fail(VAL_ERR_INVALID_ARG, "first is NULL");
+    if (!d_file_size) return fail(VAL_ERR_INVALID_ARG, "file_size is NULL");
+    if (!d_last_acked || !d_next) return fail(VAL_ERR_INVALID_ARG, "last_acked or next is NULL");
+    if (!d_base) return fail(VAL_ERR_INVALID_ARG, "base is NULL");
+    DeviceScope ds;
+    Ctx *c = nullptr;
+    if ((st = cur_dev(stream, d_last_acked, &c)) != VAL_OK) return st;
+    const hipStream_t s = pick_stream(stream);
+    uint8_t *ok = d_ok ? d_ok : (uint8_t *)d_work;
+    // 1. verify: the launches of val_crc32_verify_frames_dev
+    FrameParams f = data_frames(d_base, d_off, d_len, stride, flen, n);
+    f.verify = 1;
+    f.out_ok = ok;
+    f.nbad = d_nbad;
+    if ((st = launch_frames(*c, f, d_off ? len_hint : flen, s)) != VAL_OK) return st;
+    // 2. apply: a reduction per transfer
+    const WindowPlan plan = plan_ack(VAL_GPU_ACK_APPLY, (uint32_t)c->cus, n, n_files);
+    AckApplyParams p{};
+    p.base = d_base;
+    p.off = d_off;
+    p.len = d_len;
+    p.stride = stride;
+    p.flen = flen;
+    p.n = n;
+    p.n_files = n_files;
+    p.first = d_first;
+    p.ok = ok;
+    p.file_size = d_file_size;
+    p.last_acked = d_last_acked;
+    p.next = d_next;
+    p.nretrans = d_nretrans;
+    p.file_nbad = d_file_nbad;
+    hipLaunchKernelGGL(k_ack_apply_files, dim3(plan.launch[0].grid), dim3(kAckBlock), 0, s, p);
+    VCRC_HIP(hipGetLastError(), "k_ack_apply_files launch");
+    return VAL_OK;
+}
+
+uint32_t val_gpu_plan_ack_calls(uint32_t call, uint32_t cus, uint32_t n, uint32_t n_files, val_gpu_launch_t out[3])
+{
+    const WindowPlan plan = plan_ack(call, cus, n, n_files);
+    for (uint32_t i = 0; out && i < plan.count; i++) out[i] = plan.launch[i];
+    return plan.count;
 }
 
 val_status_t val_gpu_set_scan_front(uint32_t lanes)

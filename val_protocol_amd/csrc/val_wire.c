@@ -444,3 +444,143 @@ val_status_t val_resume_verdict(int window_ok, uint32_t local_crc, uint32_t send
         *resume_off_out = off;
     return st;
 }
+
+/* ---- DATA_ACK / DATA_NAK: the receiver's answers and the sender's handling ---- */
+void val_frame_ack_offsets(const uint8_t *stream, const uint64_t *frame_off, const uint32_t *crc_len, uint32_t n,
+                           uint8_t *kind, uint64_t *ack_off)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t *f = stream + frame_off[i];
+        const uint32_t L = crc_len[i];
+        uint8_t k = 0;
+        uint64_t off = 0;
+        if (L >= VAL_WIRE_HEADER_SIZE && (f[0] == (uint8_t)VAL_PKT_DATA_ACK || f[0] == (uint8_t)VAL_PKT_DATA_NAK)) {
+            k = f[0];
+            off = val_get_le32(f + 4);
+            if (L >= VAL_WIRE_HEADER_SIZE + 4u)
+                off |= (uint64_t)val_get_le32(f + VAL_WIRE_HEADER_SIZE) << 32;
+        }
+        if (kind)
+            kind[i] = k;
+        if (ack_off)
+            ack_off[i] = off;
+    }
+}
+
+/* The frames val_frame_accept would accept: whether frame i, judged at w, is one. */
+static int respond_accepts(uint64_t file_off, uint32_t pay_len, uint64_t w, uint64_t file_cap)
+{
+    if (file_off != VAL_FRAME_OFFSET_IMPLIED && file_off != w)
+        return 0;
+    return !(w > file_cap || (uint64_t)pay_len > file_cap - w);
+}
+
+void val_frame_respond_window(const uint64_t *file_off, const uint32_t *pay_len, const uint8_t *ok, uint32_t n,
+                              uint64_t file_cap, uint64_t total, uint32_t ack_stride, uint64_t *written,
+                              uint32_t *since, uint32_t *resp_frame, uint8_t *resp_kind, uint64_t *resp_off,
+                              uint32_t *n_resp)
+{
+    if (n_resp)
+        *n_resp = 0;
+    if (!written || (n && (!file_off || !pay_len)) || (ack_stride && !since))
+        return;
+    uint64_t w = *written;
+    /* one ACK per window: the call's last accepted frame is known only after a walk of its own */
+    uint32_t last = n;
+    if (ack_stride == 0) {
+        for (uint32_t i = 0; i < n; i++) {
+            if ((ok && !ok[i]) || file_off[i] == VAL_FRAME_OFFSET_NOT_DATA)
+                continue;
+            if (respond_accepts(file_off[i], pay_len[i], w, file_cap)) {
+                w += pay_len[i];
+                last = i;
+            }
+        }
+        w = *written;
+    }
+    uint32_t s = ack_stride ? *since : 0u;
+    uint32_t r = 0;
+#define VAL_RESPOND_EMIT(k_, off_)           \
+    do {                                     \
+        if (resp_frame)                      \
+            resp_frame[r] = i;               \
+        if (resp_kind)                       \
+            resp_kind[r] = (uint8_t)(k_);    \
+        if (resp_off)                        \
+            resp_off[r] = (off_);            \
+        r++;                                 \
+    } while (0)
+    for (uint32_t i = 0; i < n; i++) {
+        if ((ok && !ok[i]) || file_off[i] == VAL_FRAME_OFFSET_NOT_DATA)
+            continue;
+        const uint64_t eff = file_off[i] == VAL_FRAME_OFFSET_IMPLIED ? w : file_off[i];
+        if (eff == w) {
+            if (!respond_accepts(file_off[i], pay_len[i], w, file_cap))
+                continue; /* refused by capacity alone: silent */
+            w += pay_len[i];
+            if (w >= total) {
+                VAL_RESPOND_EMIT(VAL_PKT_DATA_ACK, w);
+                s = 0;
+            } else if (ack_stride == 0) {
+                if (i == last)
+                    VAL_RESPOND_EMIT(VAL_PKT_DATA_ACK, w);
+            } else {
+                if (s != UINT32_MAX)
+                    s++;
+                if (s >= ack_stride) {
+                    VAL_RESPOND_EMIT(VAL_PKT_DATA_ACK, w);
+                    s = 0;
+                }
+            }
+        } else if (eff < w) {
+            VAL_RESPOND_EMIT(VAL_PKT_DATA_ACK, w); /* duplicate: reaffirm */
+        } else {
+            VAL_RESPOND_EMIT(VAL_PKT_DATA_NAK, w); /* gap */
+            VAL_RESPOND_EMIT(VAL_PKT_DATA_ACK, w);
+        }
+    }
+#undef VAL_RESPOND_EMIT
+    *written = w;
+    if (ack_stride)
+        *since = s;
+    if (n_resp)
+        *n_resp = r;
+}
+
+void val_frame_apply_acks(const uint8_t *kind, const uint64_t *ack_off, const uint8_t *ok, uint32_t n,
+                          uint64_t file_size, uint64_t *last_acked, uint64_t *next, uint32_t *n_retrans,
+                          uint32_t *n_crc)
+{
+    uint32_t retrans = 0, crc = 0;
+    if (n_retrans)
+        *n_retrans = 0;
+    if (n_crc)
+        *n_crc = 0;
+    if (!last_acked || !next || (n && (!kind || !ack_off)))
+        return;
+    uint64_t la = *last_acked, nx = *next;
+    for (uint32_t i = 0; i < n; i++) {
+        if (ok && !ok[i]) {
+            nx = la;
+            retrans++;
+            crc++;
+            continue;
+        }
+        if (kind[i] != (uint8_t)VAL_PKT_DATA_ACK && kind[i] != (uint8_t)VAL_PKT_DATA_NAK)
+            continue;
+        if (la < ack_off[i] && ack_off[i] <= file_size)
+            la = ack_off[i];
+        if (kind[i] == (uint8_t)VAL_PKT_DATA_NAK) {
+            nx = la;
+            retrans++;
+        }
+    }
+    if (nx < la)
+        nx = la;
+    *last_acked = la;
+    *next = nx;
+    if (n_retrans)
+        *n_retrans = retrans;
+    if (n_crc)
+        *n_crc = crc;
+}

@@ -576,6 +576,182 @@ def resume_check_files_dev(file_ptr, existing, incoming, req_off, req_len, req_c
     return result, written, local_crc
 
 
+PKT_DATA_ACK, PKT_DATA_NAK = 6, 13
+NAK_REASON_GAP = 1
+
+
+def put_response(kind: int, offset: int, reason: int = NAK_REASON_GAP) -> bytes:
+    """One DATA_ACK (6) or DATA_NAK (13) frame for ``offset`` with its trailer
+    (val_frame_put_response; host only): 12 or 16 bytes for an ACK, 24 for a
+    NAK; b"" for another kind."""
+    out = (ctypes.c_uint8 * 24)()
+    used = lib().val_frame_put_response(kind, offset, reason, out)
+    return bytes(out[:used])
+
+
+def ack_offsets(stream: np.ndarray, frame_off, crc_len):
+    """Kind (6, 13 or 0) and acknowledged offset of each scanned frame
+    (val_frame_ack_offsets). Returns (kind uint8, ack_off uint64)."""
+    stream = np.ascontiguousarray(stream, dtype=np.uint8)
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    crc_len = np.ascontiguousarray(crc_len, dtype=np.uint32)
+    kind = np.zeros(crc_len.size, dtype=np.uint8)
+    off = np.zeros(crc_len.size, dtype=np.uint64)
+    lib().val_frame_ack_offsets(stream.ctypes.data, frame_off.ctypes.data, crc_len.ctypes.data, crc_len.size,
+                                kind.ctypes.data, off.ctypes.data)
+    return kind, off
+
+
+def respond_window(file_off, pay_len, written: int, total: int, ack_stride: int = 1, since: int = 0,
+                   file_cap: int = (1 << 64) - 1, ok=None):
+    """The receiver's answer to one file's window (val_frame_respond_window;
+    host only): inputs as frame_accept, plus the incoming file's size
+    ``total``, the ACK stride (0: one ACK per window) and ``since``, the frames
+    accepted since the last stride ACK. Returns (resp_frame uint32, resp_kind
+    uint8, resp_off uint64, written, since): the responses in frame order."""
+    file_off = np.ascontiguousarray(file_off, dtype=np.uint64)
+    pay_len = np.ascontiguousarray(pay_len, dtype=np.uint32)
+    n = pay_len.size
+    okp = None
+    if ok is not None:
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        okp = ok.ctypes.data
+    frame = np.zeros(2 * n, dtype=np.uint32)
+    kind = np.zeros(2 * n, dtype=np.uint8)
+    off = np.zeros(2 * n, dtype=np.uint64)
+    w, s, nr = ctypes.c_uint64(written), ctypes.c_uint32(since), ctypes.c_uint32(0)
+    lib().val_frame_respond_window(file_off.ctypes.data, pay_len.ctypes.data, okp, n, file_cap, total, ack_stride,
+                                   ctypes.byref(w), ctypes.byref(s), frame.ctypes.data, kind.ctypes.data,
+                                   off.ctypes.data, ctypes.byref(nr))
+    r = nr.value
+    return frame[:r], kind[:r], off[:r], int(w.value), int(s.value)
+
+
+def apply_acks(kind, ack_off, file_size: int, last_acked: int, next: int, ok=None):
+    """The sender's handling of one transfer's response window
+    (val_frame_apply_acks; host only): ``kind`` / ``ack_off`` from ack_offsets,
+    ``ok`` the trailer verdicts (None: all good). Returns (last_acked, next,
+    n_retrans, n_crc)."""
+    kind = np.ascontiguousarray(kind, dtype=np.uint8)
+    ack_off = np.ascontiguousarray(ack_off, dtype=np.uint64)
+    okp = None
+    if ok is not None:
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        okp = ok.ctypes.data
+    la, nx = ctypes.c_uint64(last_acked), ctypes.c_uint64(next)
+    nr, nc = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().val_frame_apply_acks(kind.ctypes.data, ack_off.ctypes.data, okp, kind.size, file_size, ctypes.byref(la),
+                               ctypes.byref(nx), ctypes.byref(nr), ctypes.byref(nc))
+    return int(la.value), int(nx.value), int(nr.value), int(nc.value)
+
+
+def respond_bytes_max(frames: int) -> int:
+    """Bound on the response bytes of a file that owns ``frames`` frames."""
+    return int(lib().val_frame_respond_bytes_max(frames))
+
+
+def respond_work_bytes(n: int) -> int:
+    """Workspace bytes respond_files_dev needs for n frames."""
+    return int(lib().val_frame_respond_work_bytes(n))
+
+
+def apply_acks_work_bytes(n: int) -> int:
+    """Workspace bytes apply_acks_files_dev needs for n frames."""
+    return int(lib().val_frame_apply_acks_work_bytes(n))
+
+
+def respond_files_dev(base, *, first, ok, accept, written, total, out, resp_off, resp_cap, ack_stride: int = 1,
+                      since=None, off=None, length=None, stride: int = 0, flen: int = 0, n=None, ndropped=None,
+                      work=None, stream=None):
+    """Answer a delivered window with DATA_ACK / DATA_NAK frames on the GPU
+    (val_frame_respond_files_dev): call it right after unpack_data_files_dev
+    on the same stream, with the same frames and ``first`` and that call's
+    ``ok``, ``accept`` and ``written``. Three launches, returns at once.
+
+    All tensors live on the GPU. ``total`` int64[S] holds the incoming files'
+    sizes; ``since`` int32[S] (needed unless ``ack_stride`` is 0) is updated in
+    place. The responses of file s go back to back to ``out[resp_off[s]:]``,
+    at most ``resp_cap[s]`` bytes (int64[S]; respond_bytes_max bounds them).
+    Returns (resp_len int64[S], nresp int32[S], ndropped int32[S]); ``out``,
+    resp_off and resp_len feed scan_streams_dev."""
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    if n is None:
+        n = int(off.numel()) if off is not None else 0
+    S = int(written.numel())
+    _per_file(S, total=total, resp_off=resp_off, resp_cap=resp_cap, since=since, ndropped=ndropped)
+    if int(first.numel()) != S + 1:
+        raise ValueError("first needs one entry more than written")
+    dev = written.device
+    resp_len = torch.zeros(S, dtype=torch.int64, device=dev)
+    nresp = torch.zeros(S, dtype=torch.int32, device=dev)
+    fresh = [resp_len, nresp]
+    if ndropped is None:
+        ndropped = torch.zeros(S, dtype=torch.int32, device=dev)
+        fresh.append(ndropped)
+    if work is None:
+        work = torch.empty(max(respond_work_bytes(n), 16), dtype=torch.uint8, device=dev)
+        fresh.append(work)
+    if stream is not None:  # allocations and zero fills are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_respond_files_dev(_dptr(base), _dptr(off), _dptr(length), stride, flen, n, S, _dptr(first),
+                                           _dptr(ok), _dptr(accept), _dptr(written), _dptr(total), ack_stride,
+                                           _dptr(since), _dptr(out), _dptr(resp_off), _dptr(resp_cap),
+                                           _dptr(resp_len), _dptr(nresp), _dptr(ndropped), _dptr(work),
+                                           int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_frame_respond_files_dev")
+    return resp_len, nresp, ndropped
+
+
+def apply_acks_files_dev(base, *, first, file_size, last_acked, next, off=None, length=None, stride: int = 0,
+                         flen: int = 0, n=None, len_hint: int = 0, nretrans=None, file_nbad=None, out_ok=None,
+                         nbad=None, work=None, stream=None):
+    """Apply a window of received DATA_ACK / DATA_NAK frames to the send state
+    of S transfers on the GPU (val_frame_apply_acks_files_dev): the verify
+    launches and one apply launch, returns at once.
+
+    All tensors live on the GPU; the frames and ``first`` as scan_streams_dev
+    returns them. ``last_acked`` and ``next`` (int64[S]) are updated in place
+    and feed fill_files_dev. ``nretrans`` / ``file_nbad`` (int32[S],
+    incremented) are allocated zeroed when not given. Returns (nretrans,
+    file_nbad)."""
+    import torch
+
+    from .crc import _dptr, _stream_ptr
+
+    if n is None:
+        n = int(off.numel()) if off is not None else 0
+    S = int(last_acked.numel())
+    _per_file(S, file_size=file_size, next=next, nretrans=nretrans, file_nbad=file_nbad)
+    if int(first.numel()) != S + 1:
+        raise ValueError("first needs one entry more than last_acked")
+    dev = last_acked.device
+    fresh = []
+    if nretrans is None:
+        nretrans = torch.zeros(S, dtype=torch.int32, device=dev)
+        fresh.append(nretrans)
+    if file_nbad is None:
+        file_nbad = torch.zeros(S, dtype=torch.int32, device=dev)
+        fresh.append(file_nbad)
+    if work is None:
+        work = torch.empty(max(apply_acks_work_bytes(n), 16), dtype=torch.uint8, device=dev)
+        fresh.append(work)
+    if stream is not None and fresh:  # allocations and zero fills are ordered before the launches
+        for t in fresh:
+            t.record_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    st = lib().val_frame_apply_acks_files_dev(_dptr(base), _dptr(off), _dptr(length), stride, flen, n, len_hint, S,
+                                              _dptr(first), _dptr(file_size), _dptr(last_acked), _dptr(next),
+                                              _dptr(nretrans), _dptr(file_nbad), _dptr(out_ok), _dptr(nbad),
+                                              _dptr(work), int(work.numel()), _stream_ptr(stream))
+    _check(st, "val_frame_apply_acks_files_dev")
+    return nretrans, file_nbad
+
+
 def payload_lens(stream: np.ndarray, frame_off, crc_len) -> np.ndarray:
     """Payload bytes of each frame (val_frame_payload_lens)."""
     stream = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -609,4 +785,7 @@ __all__ = ["serialize_header", "deserialize_header", "build_data_batch", "build_
            "fill_window", "fill_files_dev", "fill_work_bytes",
            "resume_tail_window", "resume_request_window", "resume_verdict", "file_windows_dev",
            "resume_tail_files_dev", "resume_request_files_dev", "resume_check_files_dev", "file_windows_work_bytes",
+           "put_response", "ack_offsets", "respond_window", "apply_acks", "respond_bytes_max", "respond_work_bytes",
+           "apply_acks_work_bytes", "respond_files_dev", "apply_acks_files_dev", "PKT_DATA_ACK", "PKT_DATA_NAK",
+           "NAK_REASON_GAP",
            "data_offsets", "OFFSET_IMPLIED", "OFFSET_NOT_DATA", "ValError"]

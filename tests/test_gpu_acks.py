@@ -82,9 +82,11 @@ def test_recorded_sessions_on_the_device(vc, wire, name):
 
 
 # ---- 2. constructed windows against the host rule ---------------------------------------------
-def mixed_frames(rng, n, w0, cap=U64, big=False):
-    """n explicit frames for a receiver at w0 -> (file_off, pay_len, flavour): in order, duplicate, gap,
-    corrupt ('x'), control ('c'); frames that would pass `cap` are refused and do not move the model."""
+def mixed_frames(rng, n, w0, cap=U64, big=False, implied=0.0):
+    """n frames for a receiver at w0 -> (file_off, pay_len, flavour): in order, duplicate, gap, corrupt
+    ('x'), control ('c'); frames that would pass `cap` are refused and do not move the model. Every
+    frame is explicit unless `implied` is given: the share of the in-order frames that carry no offset
+    ('i': such a frame lands wherever the receiver stands, behind a gap or a corrupt frame as well)."""
     fo, pl, fl = [], [], []
     w = w0
     for _ in range(n):
@@ -93,6 +95,8 @@ def mixed_frames(rng, n, w0, cap=U64, big=False):
         flavour = "d"
         if r < 0.6:
             off = w
+            if implied and rng.random() < implied:
+                flavour = "i"
             if w + ln <= cap:
                 w += ln
         elif r < 0.7:
@@ -111,8 +115,9 @@ def mixed_frames(rng, n, w0, cap=U64, big=False):
 
 class Receiver:
     """S receivers on the device and their host mirror. window() builds one window on the device with
-    val_frame_data_batch_dev (every frame explicit), delivers it, answers it, and compares everything
-    with the host rules; state carries over to the next window."""
+    val_frame_data_batch_dev (frames of flavour 'i' without an offset, every other frame explicit),
+    delivers it, answers it, and compares everything with the host rules; state carries over to the
+    next window. nacc and novf count what val_frame_accept accepted and refused by capacity."""
 
     def __init__(self, wire, w0, total, file_cap, stride, since, deliver=True):
         self.wire, self.S, self.stride, self.deliver = wire, len(w0), stride, deliver
@@ -125,6 +130,7 @@ class Receiver:
         self.d_since = _d32(self.since) if stride else None
         self.ndropped = torch.zeros(self.S, dtype=torch.int32, device=DEV)
         self.dropped = np.zeros(self.S, np.uint32)
+        self.nacc, self.novf = np.zeros(self.S, np.uint32), np.zeros(self.S, np.uint32)
 
     def build(self, per_file, seed, strided=0):
         """-> host copy of the stream, frame_off, crc_len (descriptor or strided slots)."""
@@ -134,12 +140,14 @@ class Receiver:
         n = pl.size
         payload = _prng.prng_bytes(seed, max(int(pl.sum()), 1))
         pay_off = (np.cumsum(pl, dtype=np.uint64) - pl).astype(np.uint64)
+        inc = np.array([x != "i" for x in fl], np.uint8) if "i" in fl else None
         if strided:
             f_off, size = np.arange(n, dtype=np.uint64) * np.uint64(strided), n * strided
         else:
-            f_off, _, size = self.wire.data_layout(pl)
+            f_off, _, size = self.wire.data_layout(pl, inc)
         out = _d8(_prng.prng_bytes(seed + 1, size + 8))
-        c_len, _, nrej = self.wire.build_data_batch_dev(_d8(payload), _d64(pay_off), _d32(pl), _d64(fo), None, out=out,
+        c_len, _, nrej = self.wire.build_data_batch_dev(_d8(payload), _d64(pay_off), _d32(pl), _d64(fo),
+                                                        None if inc is None else _d8(inc), out=out,
                                                         frame_off=None if strided else _d64(f_off), out_stride=strided)
         assert int(nrej.item()) == 0
         stream, c_len = out.cpu().numpy(), _u32(c_len)
@@ -153,25 +161,40 @@ class Receiver:
                 stream[end:end + 4] = np.frombuffer(_oracle.crc32(stream[at:end]).to_bytes(4, "little"), np.uint8)
         return stream, f_off, c_len
 
-    def window(self, per_file, seed, resp_caps, n_pad=0, strided=0):
+    def window(self, per_file, seed, resp_caps, n_pad=0, strided=0, *, loose=None, first_dev=None, n_dev=None,
+               dead=None, null_ndropped=False):
         """per_file: S tuples (file_off, pay_len, flavour); resp_caps: per file 'fit', 'short', 11, 0 or 'big';
-        n_pad: unowned padding entries (0, 0) behind the frames (descriptor mode)."""
+        n_pad: unowned padding entries (0, 0) behind the frames (descriptor mode).
+        loose: one more such tuple, frames behind the files' that no file owns. first_dev, n_dev: the
+        d_first and n the device gets instead of the files' own bounds; clamped as the contract says
+        they must give the segments of per_file. dead: {file: d_resp_off[s] of 2^60 or more}, nothing
+        is written for these files and all their responses are dropped. null_ndropped: the call gets
+        d_ndropped == NULL and the counts stay where they were."""
         wire = self.wire
-        stream, f_off, c_len = self.build(per_file, seed, strided)
+        stream, f_off, c_len = self.build(list(per_file) + ([loose] if loose else []), seed, strided)
         cnt = np.array([len(f[0]) for f in per_file])
         first = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
         n = int(first[-1])
-        ok, _ = _oracle.verify_frames(stream, f_off, c_len, nthreads=8) if n else (np.zeros(0, np.uint8), 0)
-        fo = wire.data_offsets(stream, f_off, c_len)
-        pl = wire.payload_lens(stream, f_off, c_len)
-        want, accept = [], np.zeros(n + n_pad, np.uint8)
+        n_call = (int(f_off.size) + n_pad) if n_dev is None else int(n_dev)  # the device's n
+        if first_dev is None:
+            first_dev = first
+        owned = [(min(int(a), n_call), min(max(int(a), int(b)), n_call)) for a, b in zip(first_dev[:-1], first_dev[1:])]
+        model = [(int(a), int(b)) for a, b in zip(first[:-1], first[1:])]
+        assert [x for x in owned if x[0] < x[1]] == [x for x in model if x[0] < x[1]] and n <= n_call
+        assert [x[0] < x[1] for x in owned] == [x[0] < x[1] for x in model]
+        ok, _ = _oracle.verify_frames(stream, f_off[:n], c_len[:n], nthreads=8) if n else (np.zeros(0, np.uint8), 0)
+        fo = wire.data_offsets(stream, f_off[:n], c_len[:n])
+        pl = wire.payload_lens(stream, f_off[:n], c_len[:n])
+        want, accept = [], np.zeros(n_call, np.uint8)
         for s in range(self.S):
             lo, hi = int(first[s]), int(first[s + 1])
-            dst, w_acc, _, _ = wire.frame_accept(fo[lo:hi], pl[lo:hi], self.w[s], self.file_cap[s], ok[lo:hi])
+            dst, w_acc, nacc, novf = wire.frame_accept(fo[lo:hi], pl[lo:hi], self.w[s], self.file_cap[s], ok[lo:hi])
             _, kind, off, w_new, since = wire.respond_window(fo[lo:hi], pl[lo:hi], self.w[s], self.total[s], self.stride,
                                                              self.since[s], self.file_cap[s], ok[lo:hi])
             assert w_new == w_acc
             accept[lo:hi] = dst != U64
+            self.nacc[s] += nacc
+            self.novf[s] += novf
             self.w[s] = w_new
             if self.stride and hi > lo:
                 self.since[s] = since
@@ -189,10 +212,12 @@ class Receiver:
         canvas0 = _prng.prng_bytes(seed + 2, pos + 8)
         canvas = canvas0.copy()
         w_len, w_n = np.zeros(self.S, np.uint64), np.zeros(self.S, np.uint32)
+        dead = dead or {}
+        dropped0 = self.dropped.copy()
         for s, rs in enumerate(want):
             at = 0
             for k, r in enumerate(rs):
-                if at + len(r) > caps[s]:
+                if at + len(r) > caps[s] or s in dead:
                     self.dropped[s] += len(rs) - k
                     break
                 canvas[r_off[s] + at:r_off[s] + at + len(r)] = np.frombuffer(r, np.uint8)
@@ -202,23 +227,39 @@ class Receiver:
         # the device
         base = _d8(stream)
         if strided:
-            desc = dict(stride=strided, flen=int(c_len[0]), n=n)
+            desc = dict(stride=strided, flen=int(c_len[0]), n=n_call)
         else:
             desc = dict(off=_d64(np.concatenate([f_off, np.zeros(n_pad, np.uint64)])),
-                        length=_d32(np.concatenate([c_len, np.zeros(n_pad, np.uint32)])), n=n + n_pad)
-        d_first = _d32(first)
+                        length=_d32(np.concatenate([c_len, np.zeros(n_pad, np.uint32)])), n=n_call)
+        d_first = _d32(first_dev)
         if self.deliver:
-            self.lay.unpack(wire, base, first, desc.get("off"), desc.get("length"), with_state=False,
+            self.lay.unpack(wire, base, first_dev, desc.get("off"), desc.get("length"), with_state=False,
                             **{k: v for k, v in desc.items() if k in ("stride", "flen", "n")})
             d_ok, d_acc = self.lay.ok[-1], self.lay.accept[-1]
         else:  # respond alone: the verdicts and the accepted set of the host rule, the position after them
-            d_ok, d_acc = _d8(np.concatenate([ok, np.ones(n_pad, np.uint8)])), _d8(accept)
+            d_ok, d_acc = _d8(np.concatenate([ok, np.ones(n_call - n, np.uint8)])), _d8(accept)
             self.d_written.copy_(_d64(self.w))
         out = _d8(canvas0)
-        rlen, nresp, _ = wire.respond_files_dev(base, first=d_first, ok=d_ok, accept=d_acc, written=self.d_written,
-                                                total=self.d_total, out=out, resp_off=_d64(r_off), resp_cap=_d64(caps),
-                                                ack_stride=self.stride, since=self.d_since, ndropped=self.ndropped,
-                                                **desc)
+        # a dead stream's capacity is large: the offset alone must keep every byte of it unwritten
+        d_roff = _d64([dead.get(s, o) for s, o in enumerate(r_off)])
+        d_caps = _d64([(1 << 40) if s in dead else c for s, c in enumerate(caps)])
+        if null_ndropped:  # the raw call: the wrapper would allocate the counts
+            rlen = torch.full((self.S,), -1, dtype=torch.int64, device=DEV)
+            nresp = torch.full((self.S,), -1, dtype=torch.int32, device=DEV)
+            work = torch.empty(max(wire.respond_work_bytes(n_call), 16), dtype=torch.uint8, device=DEV)
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            st = wire.lib().val_frame_respond_files_dev(
+                ptr(base), ptr(desc.get("off")), ptr(desc.get("length")), strided, desc.get("flen", 0), n_call, self.S,
+                ptr(d_first), ptr(d_ok), ptr(d_acc), ptr(self.d_written), ptr(self.d_total), self.stride,
+                ptr(self.d_since), ptr(out), ptr(d_roff), ptr(d_caps), ptr(rlen), ptr(nresp), None, ptr(work),
+                work.numel(), torch.cuda.current_stream().cuda_stream)
+            assert st == 0
+            self.dropped = dropped0
+        else:
+            rlen, nresp, _ = wire.respond_files_dev(base, first=d_first, ok=d_ok, accept=d_acc, written=self.d_written,
+                                                    total=self.d_total, out=out, resp_off=d_roff, resp_cap=d_caps,
+                                                    ack_stride=self.stride, since=self.d_since, ndropped=self.ndropped,
+                                                    **desc)
         torch.cuda.synchronize()
         assert np.array_equal(d_ok.cpu().numpy()[:n], ok) and np.array_equal(d_acc.cpu().numpy(), accept)
         assert _u64(self.d_written).tolist() == self.w
@@ -229,6 +270,8 @@ class Receiver:
         assert np.array_equal(_u32(self.ndropped), self.dropped)
         if self.stride:
             assert _u32(self.d_since).tolist() == self.since
+        # what a sender's scan and apply go on from: the device's streams, and the host rule's kept responses
+        self.last = dict(out=out, resp_off=d_roff, resp_len=rlen, kept=[rs[:int(k)] for rs, k in zip(want, w_n)])
         return want, full
 
 

@@ -100,6 +100,24 @@ def plan_case4(vc, cus):
                           flen=CASE4_FLEN)
 
 
+def plan_case4_stream(vc, cus):
+    """Case 4 with the stream loads forced on: the same launches, the first k_frames_stream out of the
+    64 partitions behind 24 static rounds, the 333-frame tail at 64 lanes on ordinary loads."""
+    n, plan = plan_case4(vc, cus)
+    vc.set_stream_loads(1)
+    try:
+        forced = vc.plan_frames(cus, n, CASE4_FLEN, flen=CASE4_FLEN)
+        loads = vc.plan_stream_loads(cus, n, CASE4_FLEN, flen=CASE4_FLEN)
+    finally:
+        vc.set_stream_loads(-1)
+    assert [l.astuple() for l in forced] == [l.astuple() for l in plan]
+    assert loads == [True, False], loads
+    m = plan[0]
+    assert (m.kernel, m.lanes, m.depth, m.qparts, m.static_rounds) == (KERNEL_FRAMES, 8, 1, 64, 24), m.astuple()
+    assert (plan[1].lanes, plan[1].count) == (64, 333), plan[1].astuple()
+    return n, plan
+
+
 CASE5_HINT, CASE5_FLEN = 1000, 349
 
 
@@ -348,7 +366,10 @@ def test_partitions_four_lanes_every_depth(vc):
 
 def test_partitions_eight_lanes_strided(vc):
     """Case 4: the smallest launch the bytes-per-wave rule gives the partitions at 8 lanes: 4,096-B
-    frames, strided, 47 rounds and 333 frames (6.3 GB at 256 CUs). CRC and header_crc, twice."""
+    frames, strided, 47 rounds and 333 frames (6.3 GB at 256 CUs). CRC and header_crc, twice. Then
+    once more over the same buffer with the stream loads forced on: k_frames_stream out of the same 64
+    partitions (by the rule the path starts at 8,192-B frames, and the shipped launches of that length
+    with partitions are as large as this one)."""
     n, plan = plan_case4(vc, _cus())
     flen, stride = CASE4_FLEN, CASE4_FLEN + 4
     g = torch.Generator(device=DEV).manual_seed(404)
@@ -362,6 +383,18 @@ def test_partitions_eight_lanes_strided(vc):
         torch.cuda.synchronize()
         assert np.array_equal(_u32(crc), want)
         assert np.array_equal(_u32(hdr), want_h)
+    plan_case4_stream(vc, _cus())
+    crc, hdr = _fresh(n), _fresh(n)
+    vc.set_stream_loads(1)
+    try:
+        before = vc.stream_load_launches()
+        vc.frames(buf, stride=stride, flen=flen, n=n, out_crc=crc, out_hdr=hdr)
+        torch.cuda.synchronize()
+        assert vc.stream_load_launches() - before == 1
+    finally:
+        vc.set_stream_loads(-1)
+    assert np.array_equal(_u32(crc), want)
+    assert np.array_equal(_u32(hdr), want_h)
     del buf
     torch.cuda.empty_cache()
 

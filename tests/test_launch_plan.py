@@ -487,6 +487,8 @@ def test_gpu_queue_shapes_reach_the_queue(knobs, cus):
     assert all(p[0].qparts == 64 and p[0].static_rounds == 4 for p in plans.values())
     n4, plan = q.plan_case4(vc, cus)
     assert (plan[0].qparts, plan[0].static_rounds, plan[0].lanes) == (64, 24, 8) and n4 * 4100 < 8 << 30
+    n4s, _ = q.plan_case4_stream(vc, cus)  # the same launches with the stream loads forced: [True, False]
+    assert n4s == n4
     for G in (2, 4, 8, 16, 32):
         n5, plan = q.plan_case5(vc, cus, G)
         assert plan[0].qparts == 0 and plan[1].first == cus * 16 * (64 // G) * 2 and plan[1].count == 100
@@ -495,6 +497,22 @@ def test_gpu_queue_shapes_reach_the_queue(knobs, cus):
     assert plan[0].lanes == 8 and plan[1].count == 77
     # and the knobs are back where the table assumes them
     assert vc.plan_frames(256, _rounds(2, 8), 600, descriptors=True)[0].astuple() == EXPECTED["u600d-r8"][0]
+
+
+@pytest.mark.parametrize("cus", [64, 256, 304])
+def test_stream_loads_meet_the_partitioned_queue_by_the_rule(knobs, cus):
+    """Shipped launches run k_frames_stream out of the 64-partition queue: a strided launch of 8,192-B
+    frames over 24 group rounds and 13 frames is, by the rule and with nothing forced, one stream-load
+    launch at 8 lanes with qparts 64, 12 static rounds and the 13 frames as in-launch tail pieces.
+    tests/test_gpu_dyn_queue.py case 4 reaches that branch on the GPU by forcing the path onto its
+    4,096-B frames; if the rule moves so that no such launch is planned, this fails."""
+    knobs()
+    n = 24 * cus * 128 + 13
+    plan = vc.plan_frames(cus, n, 8192, flen=8192)
+    assert len(plan) == 1, [l.astuple() for l in plan]
+    m = plan[0]
+    assert (m.kernel, m.lanes, m.depth, m.qparts, m.static_rounds, m.tail_n) == (2, 8, 1, 64, 12, 13), m.astuple()
+    assert vc.plan_stream_loads(cus, n, 8192, flen=8192) == [True]
 
 
 @pytest.mark.parametrize("cus", [64, 128, 256, 304])

@@ -2,6 +2,9 @@
 //
 // k_frames<G, PF>      K1/K2/K3: per-frame trailer CRC, header_crc, verify;
 //                      persistent grid, G lanes per frame, uniform geometry.
+// k_frames_stream<G>   the same for long frames read through nt LDS-DMA. Both
+//                      kernels are one scheduler body (frames_body) over two
+//                      load engines (PlainLoads, StreamLoads).
 // k_bin_* + k_frames_ragged<PF>
 //                      K5: ragged descriptor batches. Frames are counting-
 //                      sorted by length on the device (512-B buckets, longest
@@ -352,6 +355,38 @@ __device__ __forceinline__ uint32_t s4_words_from(int first, const uint32_t (&w)
     return acc;
 }
 
+// header_crc: the register after a frame's first 8 bytes, or after all bytes
+// of a shorter frame. h0, h1 are the frame's first two words, loaded early by
+// the caller (used only when L >= 8).
+template <typename SB>
+__device__ __forceinline__ uint32_t header_state(uint32_t seed, gu8 *fp, uint32_t L, uint32_t h0, uint32_t h1, const SB &sb)
+{
+    uint32_t h = seed;
+    if (L >= 8) {
+        h = s4_step(h, h0, sb);
+        h = s4_step(h, h1, sb);
+    } else {
+        for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
+    }
+    return h;
+}
+// The same with the two words loaded here, inside the L >= 8 branch: loaded
+// as arguments they would read past a frame shorter than 8 bytes.
+template <typename SB>
+__device__ __forceinline__ uint32_t header_state(uint32_t seed, gu8 *fp, uint32_t L, const SB &sb)
+{
+    if (L >= 8) return header_state(seed, fp, L, ld32(fp), ld32(fp + 4), sb);
+    return header_state(seed, fp, L, 0u, 0u, sb);
+}
+
+// Verify: compare frame f's CRC with its stored trailer, write out_ok, count nbad.
+__device__ __forceinline__ void frame_verdict(const FrameParams &p, uint64_t f, uint32_t crc, uint32_t trailer)
+{
+    const bool good = crc == trailer;
+    if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
+    if (!good && p.nbad) atomicAdd(p.nbad, 1u);
+}
+
 // Hash frame f (at base + off, L bytes) with the G lanes of this lane's group
 // (g = 0..G-1). All 64 lanes of the wave must call this together (the merge
 // tree shuffles); inactive lanes pass L = 0.
@@ -435,16 +470,7 @@ __device__ __forceinline__ uint32_t hash_frame(const FrameParams &p, uint64_t f,
     for (int o = 1; o < 64; o <<= 1) first = min(first, __shfl_xor(first, o));
     first = __builtin_amdgcn_readfirstlane(first);
     pre();
-    if (hdr) {
-        uint32_t h = seed;
-        if (L >= 8) {
-            h = s4_step(h, h0, sb);
-            h = s4_step(h, h1, sb);
-        } else {
-            for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
-        }
-        p.out_hdr[f] = h ^ p.xorout;
-    }
+    if (hdr) p.out_hdr[f] = header_state(seed, fp, L, h0, h1, sb) ^ p.xorout;
     if (R > 0) {
         // Round 0 alone can hold unit 0 (padding, seed, tiny frames) or no
         // unit; the register is still zero, so no gap step.
@@ -573,11 +599,7 @@ __device__ __forceinline__ uint32_t hash_frame(const FrameParams &p, uint64_t f,
             }
             p.out_pay[f] = pay;
         }
-        if (p.verify) {
-            const bool good = (crc == trailer);
-            if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
-            if (!good && p.nbad) atomicAdd(p.nbad, 1u);
-        }
+        if (p.verify) frame_verdict(p, f, crc, trailer);
     }
     return acc;  // lane G - 1: the frame's raw register (before xorout)
 }
@@ -675,16 +697,7 @@ __device__ __forceinline__ uint32_t hash_frame_stream(const FrameParams &p, uint
     first = __builtin_amdgcn_readfirstlane(first);
     pre();
     if (Rmax > 1u) issue(1);
-    if (hdr) {
-        uint32_t h = seed;
-        if (L >= 8) {
-            h = s4_step(h, h0, sb);
-            h = s4_step(h, h1, sb);
-        } else {
-            for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
-        }
-        p.out_hdr[f] = h ^ p.xorout;
-    }
+    if (hdr) p.out_hdr[f] = header_state(seed, fp, L, h0, h1, sb) ^ p.xorout;
     uint32_t acc = 0;
     if (R > 0) {
         if (u0 == 0 && Lg >= 4) unit0_line_shift(w0, fp, pad);
@@ -757,11 +770,7 @@ __device__ __forceinline__ uint32_t hash_frame_stream(const FrameParams &p, uint
     if (last) {
         const uint32_t crc = acc ^ p.xorout;
         if (p.out_crc) p.out_crc[f] = crc;
-        if (p.verify) {
-            const bool good = (crc == trailer);
-            if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
-            if (!good && p.nbad) atomicAdd(p.nbad, 1u);
-        }
+        if (p.verify) frame_verdict(p, f, crc, trailer);
     }
     return acc;
 }
@@ -793,6 +802,45 @@ __device__ uint32_t g_vcrc_info[4096];  // ragged: class << 16 | (L >> 6) of lan
     } while (0)
 #endif
 
+// Load engines of the uniform kernels. k_frames and k_frames_stream are one
+// scheduler body (frames_body below) that differ only in how a frame's bytes
+// reach the hash: an engine names the lanes per frame G, the round depth PF,
+// the payload-state and one-pass switches PAY and C0, the table bases and LDS
+// image that go with its hash, and the hash itself.
+template <int G_, int PF_, bool PAY_, bool C0_>
+struct PlainLoads {  // hash_frame beside the sliced tables
+    static constexpr int G = G_, PF = PF_;
+    static constexpr bool PAY = PAY_, C0 = C0_;
+    using Bases = SliceBases;
+    using Image = LdsImage;
+    static __device__ __forceinline__ Bases bases(int lane) { return slice_bases((uint32_t)(lane & 31) << 2); }
+    static __device__ __forceinline__ void issue(const FrameParams &p, Image &im) { lds_tables_issue(p.consts, im); }
+    static __device__ __forceinline__ void write(const Image &im) { lds_tables_write(im); }
+    template <typename Pre, typename Mid = NoMid>
+    static __device__ __forceinline__ uint32_t hash(const FrameParams &p, uint64_t f, bool active, uint64_t off, uint32_t L,
+                                                    int g, const Bases &sb, Pre &&pre, Mid &&mid = Mid{})
+    {
+        return hash_frame<G, PF, PAY, false, C0>(p, f, active, off, L, g, sb, G, pre, mid);
+    }
+};
+template <int G_>
+struct StreamLoads {  // hash_frame_stream beside the compact rotated tables
+    static constexpr int G = G_, PF = 1;
+    static constexpr bool PAY = false, C0 = false;
+    static_assert(kStreamLoads<G, PF, PAY>, "no stream-load instance of this shape");
+    using Bases = RotBases;
+    using Image = RotImage;
+    static __device__ __forceinline__ Bases bases(int lane) { return rot_bases(lane); }
+    static __device__ __forceinline__ void issue(const FrameParams &p, Image &im) { lds_rot_issue(p.consts, im); }
+    static __device__ __forceinline__ void write(const Image &im) { lds_rot_write(im); }
+    template <typename Pre, typename Mid = NoMid>
+    static __device__ __forceinline__ uint32_t hash(const FrameParams &p, uint64_t f, bool active, uint64_t off, uint32_t L,
+                                                    int g, const Bases &sb, Pre &&pre, Mid &&mid = Mid{})
+    {
+        return hash_frame_stream<G>(p, f, active, off, L, g, sb, pre, mid);
+    }
+};
+
 // Uniform geometry: persistent grid, each wave hashes 64/G frames per step;
 // wave w takes groups w, w + nwaves, ... The four waves of a SIMD finish in
 // age order (cfg3: 2.59 / 2.62 / 2.71 / 2.88 ms, the oldest issues first), but
@@ -801,15 +849,15 @@ __device__ uint32_t g_vcrc_info[4096];  // ragged: class << 16 | (L >> 6) of lan
 // the static deal is kept.
 // One frame group of a uniform wave: hash group f.., fetch the next group's
 // descriptors meanwhile, advance.
-template <int G, int PF, bool PAY, bool C0, typename Pre>
+template <typename E, typename Pre>
 __device__ __forceinline__ void group_pass(const FrameParams &p, uint64_t &f, uint64_t &off, uint32_t &L, uint64_t &fb,
-                                           uint64_t step, int lane, const SliceBases &sb, Pre &&pre)
+                                           uint64_t step, int lane, const typename E::Bases &sb, Pre &&pre)
 {
     const uint64_t fn = f + step;
     uint64_t off_n = 0;
     uint32_t L_n = 0;
     if (fn < p.n) frame_desc(p, fn, off_n, L_n);
-    hash_frame<G, PF, PAY, false, C0>(p, f, f < p.n, off, L, lane % G, sb, G, pre);
+    E::hash(p, f, f < p.n, off, L, lane % E::G, sb, pre);
     f = fn;
     off = off_n;
     L = L_n;
@@ -893,289 +941,152 @@ __device__ __forceinline__ void tail_pieces(const FrameParams &p, int lane, cons
     const uint64_t f = (uint64_t)p.n + t;
     gu8 *fp = gptr(p.base) + off;
     if (p.out_crc) p.out_crc[f] = crc;
-    if (p.out_hdr) {
-        uint32_t h = p.seed_rest;
-        if (L >= 8) {
-            h = s4_step(h, ld32(fp), sb);
-            h = s4_step(h, ld32(fp + 4), sb);
-        } else {
-            for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
+    if (p.out_hdr) p.out_hdr[f] = header_state(p.seed_rest, fp, L, sb) ^ p.xorout;
+    if (p.verify) frame_verdict(p, f, crc, ld32(fp + L));
+}
+
+// The scheduler of both uniform kernels, over load engine E: the deal of frame
+// groups to waves, the dynamic-tail queues, the in-launch tail pieces and the
+// exit count. (p by value, as the kernels take it: through a reference the
+// SGPR spills of twenty instances moved by -17 to +10;
+// profiles/frames_body_resource_usage.txt.)
+template <typename E>
+__device__ __forceinline__ void frames_body(const FrameParams p)
+{
+    VCRC_STAMP(0);
+    VCRC_KARG_EARLY("s"(p.consts), "s"(p.base), "s"(p.off), "s"(p.len), "s"(p.stride), "s"(p.flen), "s"(p.last_len),
+                    "s"(p.n), "s"(p.seed0), "s"(p.seed_rest), "s"(gridDim.x));
+    constexpr int G = E::G, PF = E::PF;
+    constexpr bool PAY = E::PAY, C0 = E::C0;
+    constexpr int kGroups = 64 / G;
+    const int lane = threadIdx.x & 63;
+    const typename E::Bases sb = E::bases(lane);
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    typename E::Image im;
+    E::issue(p, im);
+    PowImage pim;
+    if constexpr (PAY) lds_pow_issue(p.consts, 0, pim);
+    // Descriptors of the next frame group are fetched while this one hashes.
+    // (Loading the first group's descriptors branch-free before the blob, so
+    // the prologue overlaps the first frame loads exactly, measured slower:
+    // cfg2 -3%, 256-frame windows -9%, cfg3 -1%.)
+    uint64_t fb = wave * kGroups, f = fb + (uint64_t)(lane / G), off = 0;
+    uint32_t L = 0;
+    if (f < p.n) frame_desc(p, f, off, L);
+    // Every wave runs the first pass (lanes past the batch hash nothing): the
+    // LDS fill and the barrier sit in its hash_frame call, after the frame
+    // loads are issued. Peeled, so the LDS image's registers are dead in the
+    // loop.
+    const typename E::Image &cim = im;
+    const PowImage &cpim = pim;
+    group_pass<E>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [&cim, &cpim] {
+#ifndef VCRC_NO_LDS_FILL  // diagnostic A/B builds only (wrong CRCs): the prologue's share of small launches
+        E::write(cim);
+#endif
+        if (PAY) lds_pow_write(cpim);
+        __syncthreads();
+        VCRC_STAMP(1);
+    });
+    if (!p.qhead) {
+        while (fb < p.n) group_pass<E>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
+        if constexpr (kTailPieces<G, PF, PAY>) {
+            if (p.tail_n) tail_pieces<G, PF, C0>(p, lane, sb);
         }
-        p.out_hdr[f] = h ^ p.xorout;
+        VCRC_STAMP(2);
+        return;
     }
-    if (p.verify) {
-        const bool good = crc == ld32(fp + L);
-        if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
-        if (!good && p.nbad) atomicAdd(p.nbad, 1u);
+    // Dynamic tail: the first static_rounds group rounds are dealt as above,
+    // the rest are pulled one group at a time from a queue, so waves that run
+    // ahead (the oldest of a SIMD issue first) take more of the end. Short
+    // groups split the queue into P interleaved partitions (group part + P * k
+    // of the dynamic range), one head word each, keyed by blockIdx % P as in the
+    // ragged kernel (every partition has a workgroup: P <= gridDim.x); long
+    // groups keep one word, which evens the end out better. The last wave out
+    // re-zeroes the heads for the next launch on this stream.
+    const uint64_t dyn = (uint64_t)p.static_rounds * nwaves * kGroups;  // first frame of the queue
+    while (fb < p.n && fb < dyn) group_pass<E>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
+    const uint32_t P = min(min(p.qparts, kDynParts), gridDim.x), part = blockIdx.x % P;
+    // the lane id again from mbcnt: kept live from the entry, it was the one
+    // value k_frames<16/32, 1> spilled to scratch (a scratch kernel's waves
+    // launch later)
+    // Short groups (P > 1 partitions), one group ahead: each group's dequeue is
+    // issued when the previous group starts, and its descriptors are fetched once that group's round 0 is
+    // hashed (the mid() hook, as the ragged kernel does), so a group's first
+    // loads no longer wait for an atomic and then for its descriptors: two
+    // dependent round trips per group, which short groups (1,100-B frames:
+    // five rounds) could not hide (u1100d +3.0-3.7%, profiles/r03_ab_dyn_one_ahead_gated.log).
+    // Every wave still ends on one failed dequeue, so the exit count below is
+    // unchanged.
+    const int ql = (int)__lane_id();
+    if (P == 1u) {  // long groups: dequeue at each group's start (one ahead lost cfg4 2.5%, cfg3 0.7%: a wave
+                    // then holds a reserved long group while others run dry)
+        for (;;) {
+            uint32_t k = 0;
+            if (ql == 0) k = atomicAdd(&p.qhead[0], 1u);
+            k = __builtin_amdgcn_readfirstlane(k);
+            const uint64_t gb = dyn + (uint64_t)k * kGroups;
+            if (gb >= p.n) break;
+            const uint64_t fd = gb + (uint64_t)(ql / G);
+            uint64_t od = 0;
+            uint32_t Ld = 0;
+            if (fd < p.n) frame_desc(p, fd, od, Ld);
+            E::hash(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {});
+        }
+    }
+    uint32_t k = 0;
+    if (P > 1u && ql == 0) k = atomicAdd(&p.qhead[part * 16u], 1u);
+    // (Runs of 4 or 16 consecutive groups per partition, as the ragged kernel
+    // deals one-bucket batches, measured neutral here: -0.4 to +0.4%;
+    // profiles/r04_ab_dyn_tail_runs.log.)
+    uint64_t gb = P == 1u ? p.n : dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(k)) * kGroups;
+    uint64_t fd = gb + (uint64_t)(ql / G), od = 0;
+    uint32_t Ld = 0;
+    if (fd < p.n) frame_desc(p, fd, od, Ld);
+    while (gb < p.n) {
+        uint32_t kn = 0;
+        if (ql == 0) kn = atomicAdd(&p.qhead[part * 16u], 1u);
+        uint64_t gb_n = 0, fd_n = 0, od_n = 0;
+        uint32_t Ld_n = 0;
+        E::hash(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {}, [&] {
+            gb_n = dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(kn)) * kGroups;
+            fd_n = gb_n + (uint64_t)(ql / G);
+            if (fd_n < p.n) frame_desc(p, fd_n, od_n, Ld_n);
+        });
+        gb = gb_n;
+        fd = fd_n;
+        od = od_n;
+        Ld = Ld_n;
+    }
+    if constexpr (kTailPieces<G, PF, PAY>) {
+        if (p.tail_n) tail_pieces<G, PF, C0>(p, ql, sb);
+    }
+    VCRC_STAMP(2);
+    // Exits are counted per workgroup, after a barrier: one atomic per CU. One
+    // per wave (4,096 on one word, serialised at its atomic unit) added tens of
+    // microseconds to the end of short launches, where the waves all finish
+    // together.
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t out = atomicAdd(&p.qhead[kDynParts * 16u], 1u);
+        if (out == gridDim.x - 1u) {  // every wave is past its last dequeue
+            for (uint32_t i = 0; i < P; i++) atomicExch(&p.qhead[i * 16u], 0u);
+            atomicExch(&p.qhead[kDynParts * 16u], 0u);
+        }
     }
 }
 
 template <int G, int PF, bool PAY, bool C0 = false>
 __global__ __launch_bounds__(kBlock) void k_frames(const FrameParams p)
 {
-    VCRC_STAMP(0);
-    VCRC_KARG_EARLY("s"(p.consts), "s"(p.base), "s"(p.off), "s"(p.len), "s"(p.stride), "s"(p.flen), "s"(p.last_len),
-                    "s"(p.n), "s"(p.seed0), "s"(p.seed_rest), "s"(gridDim.x));
-    constexpr int kGroups = 64 / G;
-    const int lane = threadIdx.x & 63;
-    const SliceBases sb = slice_bases((uint32_t)(lane & 31) << 2);
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    LdsImage im;
-    lds_tables_issue(p.consts, im);
-    PowImage pim;
-    if constexpr (PAY) lds_pow_issue(p.consts, 0, pim);
-    // Descriptors of the next frame group are fetched while this one hashes.
-    // (Loading the first group's descriptors branch-free before the blob, so
-    // the prologue overlaps the first frame loads exactly, measured slower:
-    // cfg2 -3%, 256-frame windows -9%, cfg3 -1%.)
-    uint64_t fb = wave * kGroups, f = fb + (uint64_t)(lane / G), off = 0;
-    uint32_t L = 0;
-    if (f < p.n) frame_desc(p, f, off, L);
-    // Every wave runs the first pass (lanes past the batch hash nothing): the
-    // LDS fill and the barrier sit in its hash_frame call, after the frame
-    // loads are issued. Peeled, so the LDS image's registers are dead in the
-    // loop.
-    const LdsImage &cim = im;
-    const PowImage &cpim = pim;
-    group_pass<G, PF, PAY, C0>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [&cim, &cpim] {
-#ifndef VCRC_NO_LDS_FILL  // diagnostic A/B builds only (wrong CRCs): the prologue's share of small launches
-        lds_tables_write(cim);
-#endif
-        if (PAY) lds_pow_write(cpim);
-        __syncthreads();
-        VCRC_STAMP(1);
-    });
-    if (!p.qhead) {
-        while (fb < p.n) group_pass<G, PF, PAY, C0>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
-        if constexpr (kTailPieces<G, PF, PAY>) {
-            if (p.tail_n) tail_pieces<G, PF, C0>(p, lane, sb);
-        }
-        VCRC_STAMP(2);
-        return;
-    }
-    // Dynamic tail: the first static_rounds group rounds are dealt as above,
-    // the rest are pulled one group at a time from a queue, so waves that run
-    // ahead (the oldest of a SIMD issue first) take more of the end. Short
-    // groups split the queue into P interleaved partitions (group part + P * k
-    // of the dynamic range), one head word each, keyed by blockIdx % P as in the
-    // ragged kernel (every partition has a workgroup: P <= gridDim.x); long
-    // groups keep one word, which evens the end out better. The last wave out
-    // re-zeroes the heads for the next launch on this stream.
-    const uint64_t dyn = (uint64_t)p.static_rounds * nwaves * kGroups;  // first frame of the queue
-    while (fb < p.n && fb < dyn) group_pass<G, PF, PAY, C0>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
-    const uint32_t P = min(min(p.qparts, kDynParts), gridDim.x), part = blockIdx.x % P;
-    // the lane id again from mbcnt: kept live from the entry, it was the one
-    // value k_frames<16/32, 1> spilled to scratch (a scratch kernel's waves
-    // launch later)
-    // Short groups (P > 1 partitions), one group ahead: each group's dequeue is
-    // issued when the previous group starts, and its descriptors are fetched once that group's round 0 is
-    // hashed (the mid() hook, as the ragged kernel does), so a group's first
-    // loads no longer wait for an atomic and then for its descriptors: two
-    // dependent round trips per group, which short groups (1,100-B frames:
-    // five rounds) could not hide (u1100d +3.0-3.7%, profiles/r03_ab_dyn_one_ahead_gated.log).
-    // Every wave still ends on one failed dequeue, so the exit count below is
-    // unchanged.
-    const int ql = (int)__lane_id();
-    if (P == 1u) {  // long groups: dequeue at each group's start (one ahead lost cfg4 2.5%, cfg3 0.7%: a wave
-                    // then holds a reserved long group while others run dry)
-        for (;;) {
-            uint32_t k = 0;
-            if (ql == 0) k = atomicAdd(&p.qhead[0], 1u);
-            k = __builtin_amdgcn_readfirstlane(k);
-            const uint64_t gb = dyn + (uint64_t)k * kGroups;
-            if (gb >= p.n) break;
-            const uint64_t fd = gb + (uint64_t)(ql / G);
-            uint64_t od = 0;
-            uint32_t Ld = 0;
-            if (fd < p.n) frame_desc(p, fd, od, Ld);
-            hash_frame<G, PF, PAY, false, C0>(p, fd, fd < p.n, od, Ld, ql % G, sb, G, [] {});
-        }
-    }
-    uint32_t k = 0;
-    if (P > 1u && ql == 0) k = atomicAdd(&p.qhead[part * 16u], 1u);
-    // (Runs of 4 or 16 consecutive groups per partition, as the ragged kernel
-    // deals one-bucket batches, measured neutral here: -0.4 to +0.4%;
-    // profiles/r04_ab_dyn_tail_runs.log.)
-    uint64_t gb = P == 1u ? p.n : dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(k)) * kGroups;
-    uint64_t fd = gb + (uint64_t)(ql / G), od = 0;
-    uint32_t Ld = 0;
-    if (fd < p.n) frame_desc(p, fd, od, Ld);
-    while (gb < p.n) {
-        uint32_t kn = 0;
-        if (ql == 0) kn = atomicAdd(&p.qhead[part * 16u], 1u);
-        uint64_t gb_n = 0, fd_n = 0, od_n = 0;
-        uint32_t Ld_n = 0;
-        hash_frame<G, PF, PAY, false, C0>(p, fd, fd < p.n, od, Ld, ql % G, sb, G, [] {}, [&] {
-            gb_n = dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(kn)) * kGroups;
-            fd_n = gb_n + (uint64_t)(ql / G);
-            if (fd_n < p.n) frame_desc(p, fd_n, od_n, Ld_n);
-        });
-        gb = gb_n;
-        fd = fd_n;
-        od = od_n;
-        Ld = Ld_n;
-    }
-    if constexpr (kTailPieces<G, PF, PAY>) {
-        if (p.tail_n) tail_pieces<G, PF, C0>(p, ql, sb);
-    }
-    VCRC_STAMP(2);
-    // Exits are counted per workgroup, after a barrier: one atomic per CU. One
-    // per wave (4,096 on one word, serialised at its atomic unit) added tens of
-    // microseconds to the end of short launches, where the waves all finish
-    // together.
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t out = atomicAdd(&p.qhead[kDynParts * 16u], 1u);
-        if (out == gridDim.x - 1u) {  // every wave is past its last dequeue
-            for (uint32_t i = 0; i < P; i++) atomicExch(&p.qhead[i * 16u], 0u);
-            atomicExch(&p.qhead[kDynParts * 16u], 0u);
-        }
-    }
+    frames_body<PlainLoads<G, PF, PAY, C0>>(p);
 }
 
-template <int G, typename Pre>
-__device__ __forceinline__ void group_pass_stream(const FrameParams &p, uint64_t &f, uint64_t &off, uint32_t &L, uint64_t &fb,
-                                                  uint64_t step, int lane, const RotBases &sb, Pre &&pre)
-{
-    const uint64_t fn = f + step;
-    uint64_t off_n = 0;
-    uint32_t L_n = 0;
-    if (fn < p.n) frame_desc(p, fn, off_n, L_n);
-    hash_frame_stream<G>(p, f, f < p.n, off, L, lane % G, sb, pre);
-    f = fn;
-    off = off_n;
-    L = L_n;
-    fb += step;
-}
-
-// k_frames with the stream loads (hash_frame_stream) and the compact image:
-// the same deal of frame groups, dynamic tail, tail pieces and exit count.
+// k_frames with the stream loads (hash_frame_stream) and the compact image.
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_frames_stream(const FrameParams p)
 {
-    VCRC_STAMP(0);
-    VCRC_KARG_EARLY("s"(p.consts), "s"(p.base), "s"(p.off), "s"(p.len), "s"(p.stride), "s"(p.flen), "s"(p.last_len),
-                    "s"(p.n), "s"(p.seed0), "s"(p.seed_rest), "s"(gridDim.x));
-    constexpr int kGroups = 64 / G;
-    const int lane = threadIdx.x & 63;
-    constexpr int PF = 1;
-    constexpr bool PAY = false, C0 = false;
-    static_assert(kStreamLoads<G, PF, PAY>, "no stream-load instance of this shape");
-    const RotBases sb = rot_bases(lane);
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    RotImage im;
-    lds_rot_issue(p.consts, im);
-    PowImage pim;
-    if constexpr (PAY) lds_pow_issue(p.consts, 0, pim);
-    // Descriptors of the next frame group are fetched while this one hashes.
-    // (Loading the first group's descriptors branch-free before the blob, so
-    // the prologue overlaps the first frame loads exactly, measured slower:
-    // cfg2 -3%, 256-frame windows -9%, cfg3 -1%.)
-    uint64_t fb = wave * kGroups, f = fb + (uint64_t)(lane / G), off = 0;
-    uint32_t L = 0;
-    if (f < p.n) frame_desc(p, f, off, L);
-    // Every wave runs the first pass (lanes past the batch hash nothing): the
-    // LDS fill and the barrier sit in its hash_frame call, after the frame
-    // loads are issued. Peeled, so the LDS image's registers are dead in the
-    // loop.
-    const RotImage &cim = im;
-    const PowImage &cpim = pim;
-    group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [&cim, &cpim] {
-#ifndef VCRC_NO_LDS_FILL  // diagnostic A/B builds only (wrong CRCs): the prologue's share of small launches
-        lds_rot_write(cim);
-#endif
-        if (PAY) lds_pow_write(cpim);
-        __syncthreads();
-        VCRC_STAMP(1);
-    });
-    if (!p.qhead) {
-        while (fb < p.n) group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
-        if constexpr (kTailPieces<G, PF, PAY>) {
-            if (p.tail_n) tail_pieces<G, PF, C0>(p, lane, sb);
-        }
-        VCRC_STAMP(2);
-        return;
-    }
-    // Dynamic tail: the first static_rounds group rounds are dealt as above,
-    // the rest are pulled one group at a time from a queue, so waves that run
-    // ahead (the oldest of a SIMD issue first) take more of the end. Short
-    // groups split the queue into P interleaved partitions (group part + P * k
-    // of the dynamic range), one head word each, keyed by blockIdx % P as in the
-    // ragged kernel (every partition has a workgroup: P <= gridDim.x); long
-    // groups keep one word, which evens the end out better. The last wave out
-    // re-zeroes the heads for the next launch on this stream.
-    const uint64_t dyn = (uint64_t)p.static_rounds * nwaves * kGroups;  // first frame of the queue
-    while (fb < p.n && fb < dyn) group_pass_stream<G>(p, f, off, L, fb, nwaves * kGroups, lane, sb, [] {});
-    const uint32_t P = min(min(p.qparts, kDynParts), gridDim.x), part = blockIdx.x % P;
-    // the lane id again from mbcnt: kept live from the entry, it was the one
-    // value k_frames<16/32, 1> spilled to scratch (a scratch kernel's waves
-    // launch later)
-    // Short groups (P > 1 partitions), one group ahead: each group's dequeue is
-    // issued when the previous group starts, and its descriptors are fetched once that group's round 0 is
-    // hashed (the mid() hook, as the ragged kernel does), so a group's first
-    // loads no longer wait for an atomic and then for its descriptors: two
-    // dependent round trips per group, which short groups (1,100-B frames:
-    // five rounds) could not hide (u1100d +3.0-3.7%, profiles/r03_ab_dyn_one_ahead_gated.log).
-    // Every wave still ends on one failed dequeue, so the exit count below is
-    // unchanged.
-    const int ql = (int)__lane_id();
-    if (P == 1u) {  // long groups: dequeue at each group's start (one ahead lost cfg4 2.5%, cfg3 0.7%: a wave
-                    // then holds a reserved long group while others run dry)
-        for (;;) {
-            uint32_t k = 0;
-            if (ql == 0) k = atomicAdd(&p.qhead[0], 1u);
-            k = __builtin_amdgcn_readfirstlane(k);
-            const uint64_t gb = dyn + (uint64_t)k * kGroups;
-            if (gb >= p.n) break;
-            const uint64_t fd = gb + (uint64_t)(ql / G);
-            uint64_t od = 0;
-            uint32_t Ld = 0;
-            if (fd < p.n) frame_desc(p, fd, od, Ld);
-            hash_frame_stream<G>(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {});
-        }
-    }
-    uint32_t k = 0;
-    if (P > 1u && ql == 0) k = atomicAdd(&p.qhead[part * 16u], 1u);
-    // (Runs of 4 or 16 consecutive groups per partition, as the ragged kernel
-    // deals one-bucket batches, measured neutral here: -0.4 to +0.4%;
-    // profiles/r04_ab_dyn_tail_runs.log.)
-    uint64_t gb = P == 1u ? p.n : dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(k)) * kGroups;
-    uint64_t fd = gb + (uint64_t)(ql / G), od = 0;
-    uint32_t Ld = 0;
-    if (fd < p.n) frame_desc(p, fd, od, Ld);
-    while (gb < p.n) {
-        uint32_t kn = 0;
-        if (ql == 0) kn = atomicAdd(&p.qhead[part * 16u], 1u);
-        uint64_t gb_n = 0, fd_n = 0, od_n = 0;
-        uint32_t Ld_n = 0;
-        hash_frame_stream<G>(p, fd, fd < p.n, od, Ld, ql % G, sb, [] {}, [&] {
-            gb_n = dyn + ((uint64_t)part + (uint64_t)P * __builtin_amdgcn_readfirstlane(kn)) * kGroups;
-            fd_n = gb_n + (uint64_t)(ql / G);
-            if (fd_n < p.n) frame_desc(p, fd_n, od_n, Ld_n);
-        });
-        gb = gb_n;
-        fd = fd_n;
-        od = od_n;
-        Ld = Ld_n;
-    }
-    if constexpr (kTailPieces<G, PF, PAY>) {
-        if (p.tail_n) tail_pieces<G, PF, C0>(p, ql, sb);
-    }
-    VCRC_STAMP(2);
-    // Exits are counted per workgroup, after a barrier: one atomic per CU. One
-    // per wave (4,096 on one word, serialised at its atomic unit) added tens of
-    // microseconds to the end of short launches, where the waves all finish
-    // together.
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t out = atomicAdd(&p.qhead[kDynParts * 16u], 1u);
-        if (out == gridDim.x - 1u) {  // every wave is past its last dequeue
-            for (uint32_t i = 0; i < P; i++) atomicExch(&p.qhead[i * 16u], 0u);
-            atomicExch(&p.qhead[kDynParts * 16u], 0u);
-        }
-    }
+    frames_body<StreamLoads<G>>(p);
 }
 
 // ---- ragged path ------------------------------------------------------------
@@ -1541,22 +1452,9 @@ __global__ __launch_bounds__(kBlock) void k_frames_split(const FrameParams p, co
         if (wi == 0 && lane == kWavesPerBlock - 1) {
             const uint32_t crc = facc ^ p.xorout;
             if (p.out_crc) p.out_crc[f] = crc;
-            if (p.out_hdr) {
-                gu8 *fp = gptr(p.base) + off;
-                uint32_t h = q.seed0;
-                if (L >= 8) {
-                    h = s4_step(h, ld32(fp), sb);
-                    h = s4_step(h, ld32(fp + 4), sb);
-                } else {
-                    for (uint32_t i = 0; i < L; i++) h = byte_step(h, fp[i], sb);
-                }
-                p.out_hdr[f] = h ^ p.xorout;
-            }
-            if (p.verify) {
-                const bool good = crc == ld32(gptr(p.base) + off + L);
-                if (p.out_ok) p.out_ok[f] = good ? 1u : 0u;
-                if (!good && p.nbad) atomicAdd(p.nbad, 1u);
-            }
+            gu8 *fp = gptr(p.base) + off;
+            if (p.out_hdr) p.out_hdr[f] = header_state(q.seed0, fp, L, sb) ^ p.xorout;
+            if (p.verify) frame_verdict(p, f, crc, ld32(fp + L));
         }
     }
 }
